@@ -11,8 +11,19 @@ via RCCL and the boundary sweeps run on a comm stream beside the interior sweep;
 gives every rank the configured width instead ((nx*N) x ny).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--precision f64|f32] [--nx 4096 --ny 4096]
+                  [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline figure needs: set-up, prime (a fixed number of untimed steps, ~1 s
+on the M config, while the GPU clock settles), W warm-up steps, the K timed steps, the JSON line.
+The lattice starts from the seeded state and runs the same number of iterations in every run, so
+its state after the timed region is the same from run to run; `--dump-outputs DIR` writes it
+(`lat.macro()`: DIR/rho.npy [cells], DIR/u.npy [2, cells], float64; of a lattice of more than 2^21
+cells a fixed stratified sample of 2^21 cells drawn with numpy seed 12345; N > 1: every rank its
+slab, DIR/rho_rank<r>.npy, the 2^21 cells shared among the ranks).  `--full` adds what takes runs of its own: the CPU
+baseline, the finite check of the final state (`state_finite`; also done with --dump-outputs) and,
+at N > 1, the launch timing of the roofline (a follow-up phase with events).
 
 Rank 0 prints ONE JSON line.  `roofline.achieved` = algorithmic bytes of the collide-stream
 kernel (18 populations x 8 B = 144 B per cell in f64) x cells per launch / mean launch time
@@ -20,7 +31,7 @@ measured with HIP events on the stream the kernel runs on (N = 1: inside the tim
 N > 1: in a follow-up phase, so the events' cost stays out of `value`); `roofline.traffic` = HBM bytes
 per launch from rocprofv3 PMC counters (profiles/pmc_traffic.json, FETCH_SIZE doubled per
 MI355X_MICROARCH.md §HBM) when a matching profile exists.  `cpu_baseline` = the oracle
-(reference kernels restated in C, unfused AoS sequence) on the host cores, rank 0 at N=1.
+(reference kernels restated in C, unfused AoS sequence) on the host cores, rank 0 at N=1, with --full.
 """
 from __future__ import annotations
 
@@ -37,6 +48,7 @@ sys.path.insert(0, REPO)
 
 METRIC = "MLUPS and achieved-HBM-GB/s, 4096² D2Q9 channel, 1/2/4/8 MI355X"
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+PRIME_STEPS_PER_SECOND = 12600  # --prime-seconds in steps: 300 x 42, what 1 s of wall time held on the M config
 
 # BASELINE.json configs: (nx, ny, precision, Lagrangian points or None, description)
 WORKLOADS = {
@@ -104,14 +116,21 @@ def parse():
                    help="strong (default): the configured lattice over N ranks; weak: N times the "
                         "configured width (K4 weak scaling: (nx*N) x ny, one configured lattice per rank)")
     p.add_argument("--prime-seconds", type=float, default=1.0,
-                   help="untimed steps before the warmup until this much wall time has passed (the GPU "
-                        "clock settles under load; reported as `prime` in the JSON line)")
+                   help="untimed steps before the warmup, 12600 (300 x 42) per second asked for, which is ~1 s of "
+                        "the M config: a fixed count, so that every run times the same state (the GPU clock "
+                        "settles under load; reported as `prime` in the JSON line with the wall time it took)")
     p.add_argument("--frozen", action="store_true",
                    help="IB workloads: points of iteration 250 for the whole run (round-1 workload)")
     p.add_argument("--filament-offset", type=float, default=0.0,
                    help="K5: filament m stands at (m + offset) * 128 columns (0 = on every slab edge, the BASELINE "
                         "config; 0.5 = the round-2 layout, every filament mid-slab)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the state the timed steps end in (lat.macro(): rho.npy, u.npy, float64; a fixed "
+                        "seeded sample of a lattice of more than 2^21 cells) into DIR")
+    p.add_argument("--full", action="store_true",
+                   help="also what takes runs of its own: the CPU baseline, the finite check of the final state, "
+                        "at N > 1 the launch timing of the roofline (events over further steps)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     p.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU sample duration")
     p.add_argument("--no-profile-events", action="store_true", help="skip per-launch HIP events")
     p.add_argument("--rccl-self", action="store_true",
@@ -256,6 +275,28 @@ def deep_label(mean):
     lo, hi = int(mean), -(-mean // 1)
     return str(int(mean)) if lo == hi else f"{lo}/{int(hi)}"
 
+DUMP_CELLS = 1 << 21  # 2^21 cells x (rho + u_x + u_y) x 8 B = 48 MiB, under the 64 MB a dump may take
+
+
+def dump_outputs(path, rho, u, rank, world, seed):
+    """--dump-outputs: rho [n] and u [2, n] (float64) of this rank's slab as path/rho.npy, path/u.npy
+    (N > 1: rho_rank<r>.npy, u_rank<r>.npy).  A slab of more than DUMP_CELLS / world cells is sampled:
+    one cell out of each of that many equal strata of the flat cell index, its place in the stratum
+    drawn with numpy's default_rng(seed) — the same cells in every run of the same lattice."""
+    n = rho.size
+    u = u.reshape(2, n)
+    k = max(1, DUMP_CELLS // world)
+    if n > k:
+        lo = np.arange(k, dtype=np.int64) * n // k
+        hi = np.arange(1, k + 1, dtype=np.int64) * n // k
+        idx = lo + (np.random.default_rng(seed).random(k) * (hi - lo)).astype(np.int64)
+        rho, u = rho[idx], u[:, idx]
+    os.makedirs(path, exist_ok=True)
+    tag = f"_rank{rank}" if world > 1 else ""
+    np.save(os.path.join(path, f"rho{tag}.npy"), np.ascontiguousarray(rho, dtype=np.float64))
+    np.save(os.path.join(path, f"u{tag}.npy"), np.ascontiguousarray(u, dtype=np.float64))
+
+
 def main():
     a = parse()
     # Libraries (RCCL's version banner, torch) may print to fd 1: route it to stderr and keep
@@ -320,16 +361,12 @@ def main():
     # prime: the clock of an idle GPU ramps up over the first ~0.1-1 s of load; a 20-step timed
     # region (~3 ms at 4096^2) would otherwise measure the ramp (profiles/r02a_bench_*.json: 109k
     # MLUPS at 20 steps vs 125k at 500 on the same box)
-    # (ranks step together: rank 0's clock decides, broadcast after every chunk)
+    # A count of steps, not a wall time: the state the timed steps start from (and --dump-outputs
+    # writes) is then the same in every run, and so is the kernels' rate, which depends on it (the
+    # deep sweep runs the seeded noise ~2-4 % slower than the state ~12000 iterations later).
+    # PRIME_STEPS_PER_SECOND iterations take ~1 s on the M config.
     prime_steps, tp = 0, time.perf_counter()
-    while True:
-        go = time.perf_counter() - tp < a.prime_seconds
-        if distributed:
-            flag = torch.tensor([1.0 if go else 0.0], device="cpu" if rehearsal else "cuda")
-            dist.broadcast(flag, src=0)
-            go = bool(flag.item() > 0)
-        if not go:
-            break
+    for _ in range(max(0, round(a.prime_seconds * PRIME_STEPS_PER_SECOND / 42))):
         drv.run(42)  # whole deep cycles at every depth 3 ... 7
         lat.synchronize()
         prime_steps += 42
@@ -365,7 +402,17 @@ def main():
     # deep launches of the timed region and their mean depth (a call mixes depths K and K-1 so that
     # it needs no remainder launches, ctx_step.hip:deep_depth)
     deep_mean = tm["deep_iterations"] / tm["deep_launches"] if tm["deep_launches"] else float(tm["sweepk_depth"])
-    if not events_in_timed and not a.no_profile_events:
+    # the state the timed steps end in, before anything else steps the lattice (macro() is collective
+    # for an RCCL group)
+    rho_s = None
+    if a.dump_outputs or a.full:
+        rho_s, u_s = lat.macro()
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, rho_s, u_s, rank, world, W.SEED)
+    # per-launch figures exist where the timed region carried events (N = 1) or, with --full, from the
+    # follow-up phase (N > 1)
+    untimed = a.no_profile_events or (not events_in_timed and not a.full)
+    if not events_in_timed and not untimed:
         lat.set_profiling(2)
         # whole cycles only (an IB run's last n mod K iterations are one-step launches over the lattice)
         kd = int(tm["sweepk_depth"])
@@ -400,7 +447,7 @@ def main():
         launch_ms = tm["sweepk_ms"] / tm["sweepk_launches"]
         cells_per_launch = tm["sweepk_cells"] // tm["sweepk_launches"]
         iters_per_launch = round(deep_mean, 3)
-    if a.no_profile_events:  # nothing timed per launch: name the kernel from what ran
+    if untimed:  # nothing timed per launch: name the kernel from what ran
         # (the band-cycle counter is kept without events; a deep run without IB shows as no
         # one-step launches at all, since only the boot iteration and remainders are one-step)
         depth = int(tm["sweepk_depth"])
@@ -417,10 +464,9 @@ def main():
         dist.all_reduce(sl, op=dist.ReduceOp.MAX)
         launch_ms = float(sl.item())
 
-    # sanity: the state must stay finite (macro() is collective for an RCCL group)
-    rho_s, _ = lat.macro()
-    finite = bool(np.isfinite(rho_s).all())
-    if distributed:
+    # sanity (--full, --dump-outputs): the state must stay finite
+    finite = None if rho_s is None else bool(np.isfinite(rho_s).all())
+    if distributed and finite is not None:
         fin = torch.tensor([1.0 if finite else 0.0], device=red_dev)
         dist.all_reduce(fin, op=dist.ReduceOp.MIN)
         finite = bool(fin.item() > 0)
@@ -435,7 +481,7 @@ def main():
 
     if rank == 0:
         cpu = None
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             lat.close()
             cpu = cpu_baseline(nx, ny, a.cpu_seconds, points, a.frozen)
         out = {
@@ -498,7 +544,8 @@ def main():
                            if iters_per_launch > 2 else
                            "sweep2_kernel (lbm_sweep_impl.h): two iterations per launch, state read and written once"
                            if sweep else "fused_kernel (lbm_kernels.hip)")
-                          + (" — not timed (--no-profile-events)" if a.no_profile_events else ""),
+                          + (" — not timed (--no-profile-events)" if a.no_profile_events else
+                             " — not timed (N > 1 without --full)" if untimed else ""),
                 "bytes_per_cell": bytes_per_cell,
                 "cells_per_launch": cells_per_launch,
                 "iterations_per_launch": iters_per_launch,
@@ -508,6 +555,7 @@ def main():
                 "one_step_equivalent_frac": round(mlups * 1e6 * bytes_per_cell / 1e9 / HBM_PEAK_GBPS, 4),
                 "launch_ms": round(launch_ms, 5),
                 "launch_timing": ("none (--no-profile-events)" if a.no_profile_events else
+                                  "none (N > 1 without --full)" if untimed else
                                   "HIP events in the timed region" if events_in_timed else
                                   f"HIP events over {min(a.steps, 100)} further steps after the timed region"
                                   + (" (MAX over ranks)" if distributed else "")),

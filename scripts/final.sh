@@ -24,7 +24,7 @@ mkdir -p "$OUT"
   grep smoke "$OUT/smoke.log"
 }
 [ -z "$SKIP_BENCH" ] && {
-  timeout -k 10 400 python3 bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
+  timeout -k 10 400 python3 bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
   cat "$OUT/bench.json"
 }
 B="python3 bench.py --no-cpu-baseline"

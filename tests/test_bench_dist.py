@@ -25,7 +25,7 @@ def _port():
 def _run(args, world=2, timeout=240):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
            "--master-addr", "127.0.0.1", f"--master-port={_port()}", os.path.join(REPO, "bench.py"),
-           "--gpus", str(world), "--same-device", "--prime-seconds", "0.2", "--no-cpu-baseline"] + args
+           "--gpus", str(world), "--same-device", "--prime-seconds", "0.2", "--full", "--no-cpu-baseline"] + args
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd=REPO)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert p.returncode == 0 and len(lines) == 1, (p.returncode, p.stdout[-2000:], p.stderr[-4000:])
