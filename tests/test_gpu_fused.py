@@ -671,6 +671,29 @@ def test_sweep_deep_bit_identical(gpu, oracle, precision, depth, monkeypatch):
 
 
 @pytest.mark.parametrize("precision", ["f64", "f32"])
+def test_default_deep_builds(gpu, precision, monkeypatch):
+    """With no IBLB_* variable in the environment a lone slab's depth-7 sweep runs the measured build,
+    (MODE, cells per lane, waves per SIMD) of iblb_timing: the wall split with the LDS window on 300
+    rows (f64 with the preshift at one wave, f32 packed at three); on 63 rows, fewer than two wall
+    chunks hold, the unsplit walk (f32: packed)."""
+    from cuda_iblb_11_amd import workloads as W
+    for name in [n for n in os.environ if n.startswith("IBLB_")]:
+        monkeypatch.delenv(name)
+    want = {"f64": {300: (785, 2, 1), 63: (1, 2, 1)}, "f32": {300: (593, 2, 3), 63: (65, 2, 1)}}[precision]
+    for ny in (300, 63):
+        rho, u = W.perturbed_state(37, ny, 7)
+        lat = gpu.Lattice(37, ny, W.TAU, W.TAU2, precision=precision)
+        try:
+            lat.set_state(rho, u)
+            lat.step(1 + 7)
+            tm = lat.timing()
+            assert tm["deep_launches"] == 1 and tm["deep_iterations"] == 7, tm
+            assert (tm["deep_mode"], tm["deep_vs"], tm["deep_waves_per_simd"]) == want[ny], (ny, tm)
+        finally:
+            lat.close()
+
+
+@pytest.mark.parametrize("precision", ["f64", "f32"])
 def test_sweep_two_iterations_bit_identical(gpu, oracle, precision, monkeypatch):
     """The two-iteration sweep kernel (g1 kept in registers, ghost lanes for the chunk edges,
     periodic columns) equals pairs of one-step launches bit for bit, for every cells-per-lane
