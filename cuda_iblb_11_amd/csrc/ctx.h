@@ -151,7 +151,10 @@ struct iblb_ctx {
     int band_vhalf_env = 1;      // IBLB_BAND_VHALF: f32 chained chain's level launches at half-height waves
     bool band_vhalf = false;     // the installed plan's level entries are in chunks of 64 * V/2 rows
     double* bf_alloc = nullptr;  // merged chain: two more dense force buffers (levels j % 3 = 1, 2) ...
-    uint8_t* bfl_alloc = nullptr;  // ... and their chunk flags (zero between cycles)
+    uint8_t* bfl_alloc = nullptr;  // ... and their chunk flags, one per 64 * V rows.  Full-height levels clear a flag
+                                   // with the force rows they consume (zero between cycles); f32 half-height levels
+                                   // (band_vhalf) leave the flags set, here and in `flags`, since two waves read each:
+                                   // there only the force rows are zeroed, and a set flag over zero rows is harmless
     double* bfd[2] = {nullptr, nullptr};
     uint8_t* bfl[2] = {nullptr, nullptr};
     int band_par_env = 1;        // IBLB_BAND_PAR: the last level beside the deep sweep (lone and group slabs)

@@ -9,6 +9,8 @@ difference after the run are the envelope that tests/test_gpu_fused.py::test_ib_
 bounds the GPU by (2x).  Configuration = that test's: 320 x 160, 150 points in three filaments,
 perturbed initial state (seed 11), body force 1e-6, 5K + 3 = 38 iterations at K = 7.
 Test infrastructure (CPU, the oracle); the envelope is committed as tests/golden/ib_flip_envelope.json.
+run and envelope also take another lattice, step count and points function: the IB edge configurations
+(tests/ib_edges.py, tests/golden/ib_edge_envelope.json).
 """
 import numpy as np
 
@@ -41,19 +43,31 @@ def float_ulps(a, b):
     return np.abs(ia - ib)
 
 
-def run(O, mag=0.0, seed=0, steps=STEPS):
-    """The oracle over `steps` iterations; populations perturbed by mag before every iteration."""
+def run(O, mag=0.0, seed=0, steps=STEPS, *, nx=NX, ny=NY, points_at=None, state_seed=11, marks=()):
+    """The oracle over `steps` iterations; populations perturbed by mag before every iteration.
+    Default: this module's configuration (static points()).  points_at(it) -> (s, u_s, epsilon) gives
+    another lattice its points per iteration (none where s is empty); the fields after the iterations
+    in `marks` are kept in sim.snaps as (rho, u) copies."""
     from cuda_iblb_11_amd import workloads as W
-    rho, u = W.perturbed_state(NX, NY, 11)
-    sim = O.Simulation(NX, NY, W.TAU, W.TAU2, rho=rho, u=u, body_force=(1e-6, 0.0))
-    sim.set_lagrangian(*points())
+    rho, u = W.perturbed_state(nx, ny, state_seed)
+    sim = O.Simulation(nx, ny, W.TAU, W.TAU2, rho=rho, u=u, body_force=(1e-6, 0.0))
+    if points_at is None:
+        sim.set_lagrangian(*points())
     g = np.random.default_rng(seed)
     fs = []
-    for _ in range(steps):
-        if mag:
-            sim.f[:] = sim.f * (1 + mag * g.integers(-2, 3, sim.f.size))
+    sim.snaps = []
+    buf = np.empty(sim.f.size)
+    for it in range(steps):
+        if points_at is not None:
+            sim.set_lagrangian(*points_at(it))
+        if mag:  # f *= 1 + mag * n, without temporaries (the same operations in the same order)
+            np.multiply(g.integers(-2, 3, sim.f.size), mag, out=buf)
+            buf += 1
+            sim.f *= buf
         sim.step(1)
         fs.append(sim.F_s.copy())
+        if it + 1 in marks:
+            sim.snaps.append((sim.rho.copy(), sim.u.copy()))
     return sim, fs
 
 
@@ -64,16 +78,34 @@ def field_rel(x, y):
                float(np.max(np.abs(x.u - y.u)) / np.max(np.abs(y.u))))
 
 
-def envelope(O):
-    """{mag: [(F_s ulps max, first iteration with a flip or -1, field difference), ...per seed]}"""
-    ref, fref = run(O)
+def _rel_fields(rho, u, rho_ref, u_ref):
+    """max over rho - 1, u_x, u_y, each over its own maximum (what the edge tests assert on the GPU)"""
+    n = rho.size
+    return max(float(np.max(np.abs((rho - 1) - (rho_ref - 1))) / np.max(np.abs(rho_ref - 1))),
+               float(np.max(np.abs(u[:n] - u_ref[:n])) / np.max(np.abs(u_ref[:n]))),
+               float(np.max(np.abs(u[n:] - u_ref[n:])) / np.max(np.abs(u_ref[n:]))))
+
+
+def envelope(O, *, seeds=SEEDS, steps=STEPS, marks=None, **config):
+    """{mag: [(F_s ulps max, first iteration with a flip or -1, field difference), ...per seed]}
+    Default: this module's configuration.  config (nx, ny, points_at, state_seed) and steps: another one
+    (run); with marks, "fields" is the maximum over the fields after those iterations and "fields_at"
+    lists them."""
+    kw = dict(config, marks=tuple(marks)) if marks else config
+    ref, fref = run(O, steps=steps, **kw)
     out = {}
     for mag in MAGS:
         rows = []
-        for seed in SEEDS:
-            b, fb = run(O, mag, seed)
-            ul = [int(float_ulps(x, y).max()) for x, y in zip(fref, fb)]
+        for seed in seeds:
+            b, fb = run(O, mag, seed, steps, **kw)
+            ul = [int(float_ulps(x, y).max()) if x.size else 0 for x, y in zip(fref, fb)]
             first = next((i for i, v in enumerate(ul) if v > 0), -1)
-            rows.append({"seed": seed, "fs_ulps": max(ul), "first_flip": first, "fields": field_rel(b, ref)})
+            row = {"seed": seed, "fs_ulps": max(ul), "first_flip": first}
+            if marks:
+                row["fields_at"] = [_rel_fields(*x, *y) for x, y in zip(b.snaps, ref.snaps)]
+                row["fields"] = max(row["fields_at"])
+            else:
+                row["fields"] = field_rel(b, ref)
+            rows.append(row)
         out[repr(mag)] = rows
     return out

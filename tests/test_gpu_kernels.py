@@ -107,8 +107,46 @@ def _points(rng, ns, X, spacing):
     return s, u_s, eps
 
 
+def _edge_points(rng, ns, X, Y, spacing):
+    """_points with some of them moved onto the lattice edges: rows y0 = 0 (node row -1: flat index j < 0,
+    skipped) and y0 = Y-1 (node row Y: j >= size, skipped; clipped in spread), the corners (0, 0) (node
+    (-1, 0) has j = -1, node (-1, 1) reads (X-1, 0)) and (X-1, Y-1) (node (X, Y-1) has j = size, node
+    (X, Y-2) reads (0, Y-1)), and half-integer coordinates with one float ulp to either side (ties-to-even
+    of nearbyint, delta at |d| = 1.5 exactly).  At spacing 4 no cell is reached by more than two points, so
+    the atomics' order cannot show."""
+    f32 = np.float32
+    s, u_s, eps = _points(rng, ns, X, spacing)
+    s[1] = 0.3                                  # point 0 (x = 0.3): corner x0 = 0, y0 = 0
+    s[4], s[5] = X - 0.7, Y - 1.2               # corner x0 = X-1, y0 = Y-1
+    s[13], s[15], s[17] = 0.2, Y - 1.0, Y - 1.4  # y0 = 0, y0 = Y-1 twice (on the row, below it)
+    for k, (dx, y) in zip(range(11, 15), [(0.5, 60.5), (1.5, 61.5), (0.5, 62.5), (1.5, 63.5)]):
+        s[2 * k], s[2 * k + 1] = np.rint(s[2 * k]) + dx, y
+    s[26], s[27] = np.nextafter(s[26], f32(0)), np.nextafter(s[27], f32(0))
+    s[28], s[29] = np.nextafter(s[28], f32(np.inf)), np.nextafter(s[29], f32(np.inf))
+    eps[8] = 0
+    return s, u_s, eps
+
+
 @pytest.mark.parametrize("spacing", [4.0, 0.7])
 def test_interpolate_spread(gpu, oracle, spacing):
+    _interpolate_spread(oracle, spacing, _points)
+
+
+@pytest.mark.parametrize("spacing", [4.0, 0.7])
+def test_interpolate_spread_lattice_edges(gpu, oracle, spacing):
+    """The drop-in interpolate and spread with points on rows 0 and Y-1, in two corners and on half-integers
+    (_edge_points): the flat index's j < 0 and j >= size skips and the spread's clipping at a corner."""
+    Xs, Ys = 96, 192
+    s = _edge_points(np.random.default_rng(4), 20, Xs, Ys, spacing)[0]
+    x0, y0 = np.rint(s[0::2]).astype(int), np.rint(s[1::2]).astype(int)
+    for corner in ((0, 0), (Xs - 1, Ys - 1)):
+        assert any((a, b) == corner for a, b in zip(x0, y0)), corner
+    assert (y0 == 0).sum() >= 2 and (y0 == Ys - 1).sum() >= 3
+    assert np.all(s[22:26] % 1 == 0.5) and np.all(s[26:28] % 1 < 0.5) and np.all(s[28:30] % 1 > 0.5)
+    _interpolate_spread(oracle, spacing, lambda rng, ns, X, sp: _edge_points(rng, ns, X, Ys, sp))
+
+
+def _interpolate_spread(oracle, spacing, points):
     from cuda_iblb_11_amd import kernels as K
     Xs, Ys = 96, 192
     rng = np.random.default_rng(4)
@@ -117,7 +155,7 @@ def test_interpolate_spread(gpu, oracle, spacing):
     rho = 1.0 + 1e-3 * rng.uniform(-1, 1, n)
     u = 1e-3 * rng.uniform(-1, 1, 2 * n)
     f = rng.uniform(0.01, 0.5, 9 * n)
-    s, u_s, eps = _points(rng, ns, Xs, spacing)
+    s, u_s, eps = points(rng, ns, Xs, spacing)
     Fso = np.zeros(2 * ns, dtype=np.float32)
     oracle.interpolate(rho, u, ns, u_s, Fso, s, Xs, Ys)
     forceo, uo, Qo = np.zeros(2 * n), u.copy(), np.zeros(1)

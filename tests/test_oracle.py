@@ -333,6 +333,52 @@ def test_ib_flip_envelope(oracle):
     assert fix["max_fs_ulps"] == max(r["fs_ulps"] for rows in env.values() for r in rows)
 
 
+def test_ib_edge_envelope(oracle):
+    """The envelopes the IB edge tests (tests/test_gpu_ib_edges.py) bound the GPU by, pinned: the oracle
+    against itself, perturbed as in test_ib_flip_envelope, on the static wall-and-corner points (384 x 131,
+    384 x 257, 1 + 6K + 2 iterations) and on the moving filaments with their removal and return (384 x 601,
+    1 + 8K + 1, 1 + 3K and 2K + 1 iterations; fields after each phase).  Reproduces
+    tests/golden/ib_edge_envelope.json (tests/golden/make_ib_edge_envelope.py; four seeds per magnitude,
+    this test reruns them all).  Every envelope stays under a tenth of the north-star 1e-6; with the points
+    gone the oracle's force is the body force alone and F_s is empty."""
+    import sys
+    sys.path.insert(0, os.path.join(HERE, "golden"))
+    try:
+        import make_ib_edge_envelope as gen
+    finally:
+        sys.path.pop(0)
+    import ib_edges
+    import ib_flips
+    fix = json.load(open(os.path.join(HERE, "golden", "ib_edge_envelope.json")))
+    threads = oracle.load().oracle_get_threads()
+    oracle.set_threads(min(8, os.cpu_count() or 1))  # (the oracle's results do not depend on its thread count)
+    try:
+        new = gen.build(oracle)
+        nx, ny, state_seed, _, points_at, _ = ib_edges.configs()["moving_384x601"]
+        sim, fs = ib_flips.run(oracle, steps=ib_edges.PHASE_A + 1, nx=nx, ny=ny, points_at=points_at, state_seed=state_seed)
+    finally:
+        oracle.set_threads(threads)
+    assert fs[-2].size == 240 and fs[-1].size == 0
+    assert np.all(sim.force[:nx * ny] == 1e-6) and np.all(sim.force[nx * ny:] == 0.0)
+    assert np.isfinite(sim.f).all() and np.max(np.abs(sim.u)) < 5e-3  # (the run is tame: u_s ~ 1e-3)
+    assert set(new["configs"]) == set(fix["configs"]) == {"static_384x131", "static_384x257", "moving_384x601"}
+    for name, got in new["configs"].items():
+        want = fix["configs"][name]
+        assert got["config"] == want["config"], name
+        for mag, rows in got["runs"].items():
+            assert len(rows) == len(want["runs"][mag]) == len(ib_edges.SEEDS)
+            for r, g in zip(rows, want["runs"][mag]):
+                assert r["seed"] == g["seed"] and r["fs_ulps"] == g["fs_ulps"] and r["first_flip"] == g["first_flip"], (name, mag, r, g)
+                assert np.allclose(r["fields_at"], g["fields_at"], rtol=1e-3, atol=0), (name, mag, r, g)
+        allrows = [r for rows in got["runs"].values() for r in rows]
+        assert want["max_fs_ulps"] == max(r["fs_ulps"] for r in allrows)
+        assert want["max_fields"] == max(r["fields"] for r in [x for rs in want["runs"].values() for x in rs])
+        assert want["max_fields"] == max(want["max_fields_at"]) <= fix["cap"] == 1e-7, name
+    cfg = fix["configs"]["moving_384x601"]["config"]
+    assert cfg["steps"] == ib_edges.MOVING_STEPS and cfg["points"] == [0, 80, 120]
+    assert cfg["fields_after"] == [ib_edges.PHASE_A, ib_edges.PHASE_A + ib_edges.PHASE_B, ib_edges.MOVING_STEPS]
+
+
 def test_f32_model_tracks_oracle(oracle):
     """tests/f32_model.py (the float32 floor the GPU f32 parity is judged against) is the oracle's
     iteration: 11 iterations from a perturbed 64 x 48 channel agree to float32 rounding."""
