@@ -69,14 +69,12 @@ struct iblb_ctx {
     long fplane = 0;  // plane stride of the dense force and the boot fields: (ncol + 2 gc) * rows
     int device = 0;
     // kernel configuration: measured defaults; the IBLB_* knobs of INTEGRATION.md §4
-    int variant = 0;            // one-step collide variant (IBLB_FUSED_VARIANT)
     bool sweep_on = true;       // multi-iteration sweeps (IBLB_SWEEP)
     int sweep_w = 4, sweep_vs = 2;  // two-iteration sweeps: columns per wave, cells per lane
     int sweep_depth = 5;        // K iterations per deep launch (IBLB_SWEEP_DEPTH; 2 = two-step only)
-    int deep_w = 96, deep_vs = 2, deep_variant = 1, deep_balance = 1;  // IBLB_DEEP_W / _VS / _VARIANT / _BALANCE
+    int deep_w = 96, deep_vs = 2, deep_balance = 1;  // IBLB_DEEP_W / _VS / _BALANCE
+    iblb::DeepBuild deep_build{};  // the deep sweeps' build features (iblb_ctx.hip: the measured default; IBLB_DEEP_BUILD)
     int slab_vs = 1;            // cells per lane of a group slab's deep sweeps
-    int int_variant = -1;       // deep variant of a group slab's interior sweep (IBLB_INTERIOR_VARIANT; -1: deep_variant)
-    int edge_trim = 0;          // slab interiors: first / last sweep narrower by this (IBLB_EDGE_TRIM)
     int reserved_cus = 0, ncu = 0;  // CUs kept free of the compute stream (RCCL groups), device CUs
     std::vector<uint32_t> comp_mask;  // the compute stream's CU mask when reserved_cus > 0
     hipStream_t stream = nullptr;
@@ -142,9 +140,6 @@ struct iblb_ctx {
     hipEvent_t band_end = nullptr; // recorded on the deep stream at the end of the last band cycle
     char* s_alloc = nullptr;     // two scratch population buffers of the trapezoid (layout of g)
     void* sbuf[2] = {nullptr, nullptr};
-    int probe_level = 0;         // timing probe IBLB_PROBE_LEVEL (lbm_kernels.hip:band_level_kernel)
-    int wrap_split = 1;          // IBLB_WRAP_SPLIT: image groups of their own for points at the x edge (wrap_range)
-    int band_deep_variant = -1;  // IBLB_BAND_DEEP_VARIANT: the band cycle's deep variant (-1: band_deep's choice)
     int band_merge = 1;          // IBLB_BAND_MERGE: 1 auto, 2 always, 0 never: each level's launch also
                                  // evaluates the next level's force (merged chain)
     bool band_merged = false;    // the installed plan runs the merged chain

@@ -418,16 +418,16 @@ static int band_deep(iblb_ctx* c, int K, hipStream_t ds) {
     // packed builds (two waves of 191 / 228 VGPRs) measured 209k / 202k vs 215k (profiles/r04/pack)
     // -- except where the chain has CUs of its own beside a long deep sweep (band_own_build, depth
     // >= 7: K5 243k vs 222k MLUPS, profiles/r04/k5var).
-    // f64: the configured variant (its wall split keeps one wave per SIMD; not with PAR's skip boxes)
-    // without the LDS window (bit 7): its 144 KB per workgroup would keep the chain's LDS-using
+    // f64: the wall split (it keeps one wave per SIMD; not with PAR's skip boxes) without the LDS
+    // window: its 144 KB per workgroup would keep the chain's LDS-using
     // kernels off the deep sweep's CUs (K3 136.0 / 137.1k vs 137.5 / 140.9k MLUPS, profiles/r04/ldswin)
-    // f32 group slab (one cell per lane, the chain on CUs of its own): the wall split + preshift, which
+    // f32 group slab (one cell per lane, the chain on CUs of its own): the wall split, which
     // takes the skip regions too (round 5, lbm_sweep_impl.h: SPLIT_SKIP)
-    d.variant = sizeof(T) == 8       ? c->deep_variant & ~128
-                : c->band_own_build ? c->deep_variant
-                : slab              ? c->deep_variant & ~(128 | 8)
-                                    : c->deep_variant & 1;
-    if (c->band_deep_variant >= 0) d.variant = c->band_deep_variant;  // (A/B: IBLB_BAND_DEEP_VARIANT)
+    constexpr DeepBuild split_only{true, false, false}, plain{false, false, false};
+    d.build = sizeof(T) == 8       ? split_only
+              : c->band_own_build ? c->deep_build  // (the context's default)
+              : slab              ? split_only
+                                  : plain;
     d.cus = c->ncu ? (slab ? c->ncu - c->reserved_cus : c->ncu) - std::max(0, c->band_reserve) : 0;
     if (c->band_flux >= 0) {
         d.fskip0 = c->band_fy0;
@@ -524,7 +524,7 @@ static int band_chain(iblb_ctx* c, int K, const T* A, T* B, T* const S[2], bool 
     int clo0, chi0;
     force_clip(c, 0, merged, &clo0, &chi0);
     int wlo = 0, whi = 0;
-    if (c->wrap_split) wrap_range(c, &wlo, &whi);
+    wrap_range(c, &wlo, &whi);
     if (c->ib_state == IB_PENDING) {  // force^t from g^t
         size_t ev = 0;
         if ((rc = ev_begin(c, &ev, bs))) return rc;
@@ -568,8 +568,6 @@ static int band_chain(iblb_ctx* c, int K, const T* A, T* B, T* const S[2], bool 
         a.Q = c->d_Q;
         a.c = c->coef;
         a.k = c->kc;
-        a.variant = c->variant;
-        a.probe = c->probe_level;
         if (merged) {
             if (j > 0) {  // the force of level j-1, read by the previous launch
                 a.fdclr = fd[(j - 1) % 3];
@@ -710,7 +708,8 @@ static int band_step(iblb_ctx* c) {
     auto boundary = [&]() -> int {
         Sweep2Args<T> b = sweep_args<T>(c, 0, c->ncol - K, c->ncol, 2, K);  // [0, K) and [ncol-K, ncol)
         b.vs = c->slab_vs;
-        b.variant = c->deep_variant & ~128;  // beside the chain: no LDS window (above)
+        b.build = c->deep_build;
+        b.build.window = false;  // beside the chain: no LDS window (above)
         if (c->band_flux >= 0) {
             b.fskip0 = c->band_fy0;
             b.fskip1 = c->band_fy1;

@@ -168,7 +168,6 @@ static int launch_fused_step(iblb_ctx* c, int col_begin, int ncols, int col_step
     a.Q = c->d_Q;
     a.c = c->coef;
     a.k = c->kc;
-    a.variant = c->variant;
     size_t ev = 0;
     int rc = timed ? ev_begin(c, &ev, st) : IBLB_OK;
     if (rc) return rc;
@@ -280,7 +279,6 @@ Sweep2Args<T> sweep_args(iblb_ctx* c, int col_begin, int col_step, int col_end, 
     a.nsweep = nsweep;
     a.W = W;
     a.vs = c->sweep_vs;
-    a.variant = 1;  // nontemporal stores
     const int fc = c->cfg.flux_column - c->x_begin;
     a.flux_col = (fc >= 0 && fc < c->ncol) ? fc : -1;
     a.fskip0 = a.fskip1 = 0;
@@ -360,7 +358,7 @@ static int sweepk_step(iblb_ctx* c, int d) {
     // balanced sweep widths (col_step 0: the launcher sizes the sweeps to whole rounds of waves)
     Sweep2Args<T> a = sweep_args<T>(c, 0, c->deep_balance ? 0 : W, c->ncol, (c->ncol + W - 1) / W, W);
     a.vs = c->deep_vs;
-    a.variant = c->deep_variant;
+    a.build = c->deep_build;
     size_t ev = 0;
     hipEvent_t e0, e1;  // timing on the launch's own signals (profiling only)
     int rc = ev_kernel(c, &ev, &e0, &e1);
@@ -445,12 +443,11 @@ static int deep_slab_step(iblb_ctx* c, int K) {
         Sweep2Args<T> a = sweep_args<T>(c, K, c->deep_balance ? 0 : W, c->ncol - K, (ni + W - 1) / W, W);
         a.vs = c->slab_vs;
         a.cus = c->ncu - c->reserved_cus;  // the compute stream's CU mask
-        a.variant = c->int_variant >= 0 ? c->int_variant : c->deep_variant;
+        a.build = c->deep_build;
         int nedge = 0;
         if (hs) {
             a.wait_lo = lo;
             a.wait_hi = hi;
-            a.edge_trim = c->edge_trim;
             if (!one_way(c)) {
                 a.done_cnt = c->sig + 16;  // (the done word: its own 64-byte line)
                 a.edge_waves = &nedge;
@@ -476,7 +473,7 @@ static int deep_slab_step(iblb_ctx* c, int K) {
     auto boundary = [&](hipEvent_t stop) -> int {
         Sweep2Args<T> b = sweep_args<T>(c, 0, c->ncol - K, c->ncol, 2, K);  // [0, K) and [ncol-K, ncol)
         b.vs = c->slab_vs;
-        b.variant = c->deep_variant;
+        b.build = c->deep_build;
         if (flag && !one_way(c)) {  // every wave waits for interior(t-K)'s edge waves
             b.wait_seq = c->sig + 16;
             b.wait_val = done_prev;
@@ -902,8 +899,8 @@ int iblb_attach_rccl(iblb_ctx* c, const char id[IBLB_UNIQUE_ID_BYTES], int nrank
         long reserve = 8;
         if (c->sweep_depth >= 3) {
             int nch = 0;
-            const int wpc = is_f64(c) ? sweepk_geometry<double>(c->sweep_depth, c->slab_vs, c->deep_variant, true, c->ny, &nch)
-                                      : sweepk_geometry<float>(c->sweep_depth, c->slab_vs, c->deep_variant, true, c->ny, &nch);
+            const int wpc = is_f64(c) ? sweepk_geometry<double>(c->sweep_depth, c->slab_vs, true, c->ny, &nch)
+                                      : sweepk_geometry<float>(c->sweep_depth, c->slab_vs, true, c->ny, &nch);
             if (wpc > 0) {
                 const long need = std::max(8L, (long)((2 * nch + wpc - 1) / wpc));
                 const long xcd = std::max(1, c->ncu / 8);
@@ -947,8 +944,6 @@ int iblb_attach_rccl(iblb_ctx* c, const char id[IBLB_UNIQUE_ID_BYTES], int nrank
         // write-through stores cost what the interior's event did), two-way in f32 (1024 x 2048: 0.01094-
         // 0.0110 vs 0.01125), profiles/r05/hs3
         c->edge_flag = (int)env_long("IBLB_EDGE_FLAG", is_f64(c) ? 2 : 1);
-        c->int_variant = (int)env_long("IBLB_INTERIOR_VARIANT", -1);
-        c->edge_trim = (int)std::max(0L, env_long("IBLB_EDGE_TRIM", 0));
         if (!c->sig) {
             int rc = alloc_zero(c, (void**)&c->sig, 128);  // signal word, done word (+64 B)
             if (rc) return rc;

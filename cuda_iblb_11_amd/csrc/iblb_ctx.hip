@@ -252,6 +252,24 @@ static int check_slab_points(iblb_ctx* c, size_t np, const float* s) {
     return IBLB_OK;
 }
 
+// IBLB_DEEP_BUILD: a comma list of split, pack, window, or the one word plain (no feature)
+static bool parse_deep_build(const char* e, DeepBuild* out) {
+    const std::string v(e);
+    DeepBuild b{false, false, false};
+    if (v != "plain")
+        for (size_t i = 0; i <= v.size();) {
+            const size_t j = std::min(v.find(',', i), v.size());
+            const std::string w = v.substr(i, j - i);
+            if (w == "split") b.split = true;
+            else if (w == "pack") b.pack = true;
+            else if (w == "window") b.window = true;
+            else return false;
+            i = j + 1;
+        }
+    *out = b;
+    return true;
+}
+
 }  // namespace iblbh
 
 using namespace iblbh;
@@ -308,6 +326,18 @@ int iblb_create(const iblb_config* cfg, iblb_ctx** out) {
     const int nc = cfg->x_count > 0 ? cfg->x_count : cfg->nx;
     if (xb < 0 || xb + nc > cfg->nx) return fail(nullptr, IBLB_ERR_ARG, "slab outside the lattice");
     if (cfg->max_points < 0) return fail(nullptr, IBLB_ERR_ARG, "max_points < 0");
+    // The deep sweeps' build: the wall split (M f64 0.480 vs 0.521 ms per launch,
+    // profiles/r04/split64; f32 one-cell group slabs: self ring 512 x 4096 0.01158 vs 0.01242 ms/iteration,
+    // 2048 x 2048 0.0187 vs 0.0210, profiles/r04/depth), in f32 with the packed collide (profiles/r04/pack),
+    // and the LDS window (f64: M 0.621 vs 0.633 ms per depth-7 launch, 512-column self ring 0.0159 vs 0.0163
+    // ms/iteration, profiles/r04/ldswin; f32, round 5: two of the three moving populations in LDS, 165
+    // VGPRs, three waves per SIMD: M f32 0.361 vs 0.387 ms per launch, 320k vs 300k MLUPS, K5 249k vs
+    // 237k, profiles/r05/f32lw; group slabs with one cell per lane ignore it).
+    // IBLB_DEEP_BUILD (the bit-identity test's knob): a comma list of split, pack, window, or plain.
+    DeepBuild deep_build{true, cfg->precision == IBLB_PREC_F32, true};
+    if (const char* e = std::getenv("IBLB_DEEP_BUILD"))
+        if (!parse_deep_build(e, &deep_build))
+            return fail(nullptr, IBLB_ERR_ARG, "IBLB_DEEP_BUILD: expected a comma list of split, pack, window, or plain");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail(nullptr, IBLB_ERR_NODEVICE, "no HIP device visible (the HIP path has no CPU fallback)");
@@ -326,47 +356,27 @@ int iblb_create(const iblb_config* cfg, iblb_ctx** out) {
     c->nch = chunks_per_column(c->ny, c->V);
     c->device = cfg->device;
     c->max_points = cfg->max_points;
-    // kernel defaults measured on MI355X: one-step variant f64 = DPP row shift +
-    // nontemporal stores (5), f32 = nontemporal loads and stores (3); two-step sweeps 16 B per lane
+    // kernel defaults measured on MI355X: two-step sweeps 16 B per lane
     // (f64 2 cells, f32 4) over 4 / 6 columns; deep sweeps K = 7 (round 4, profiles/r04/depth: M f64
     // 171k / 174k / 182k MLUPS at K = 5 / 6 / 7, f32 255k / 280k / 304k; K = 8 dropped), 2 cells per
     // lane, ~96 (f64) / ~64
     // (f32) columns balanced to whole rounds of resident waves, the linear wave order dealt to the
     // XCDs in contiguous ranges (map 2) with alternate sweeps walking towards each other
-    c->variant = (int)env_long("IBLB_FUSED_VARIANT", f64 ? 5 : 3);
     c->sweep_on = env_long("IBLB_SWEEP", 1) != 0;
     c->sweep_w = (int)env_long("IBLB_SWEEP_W", f64 ? 4 : 6);
     c->sweep_vs = (int)env_long("IBLB_SWEEP_VS", f64 ? 2 : 4);
     c->sweep_depth = (int)std::min(7L, std::max(2L, env_long("IBLB_SWEEP_DEPTH", 7)));
     c->deep_w = (int)env_long("IBLB_DEEP_W", f64 ? 96 : 64);
     c->deep_vs = (int)env_long("IBLB_DEEP_VS", 2);
-    // f32: the wall split (variant bit 1) with the packed collide (bit 3), profiles/r04/pack, and on
-    // one-cell group slabs the split with the preshift (bits 5, 6: 107 = 11 | 32 | 64; self ring
-    // 512 x 4096 0.01158 vs 0.01242 ms/iteration, 2048 x 2048 0.0187 vs 0.0210, profiles/r04/depth);
-    // f64: the wall split with the level-1 preshift (bits 1, 5: M f64 0.480 vs 0.521 ms per launch,
-    // profiles/r04/split64) and the LDS window (bit 7: 163 = 35 | 128; M f64 0.621 vs 0.633 ms per
-    // depth-7 launch, 512-column self ring 0.0159 vs 0.0163 ms/iteration, profiles/r04/ldswin)
-    // f32, round 5: bit 7 on the packed two-cell walk keeps two of the three moving populations in LDS
-    // (165 VGPRs: three waves per SIMD; 235 = 107 | 128): M f32 0.361 vs 0.387 ms per launch, 320k vs
-    // 300k MLUPS, K5 249k vs 237k (profiles/r05/f32lw); group slabs (one cell per lane) ignore it
-    c->deep_variant = (int)env_long("IBLB_DEEP_VARIANT", f64 ? 163 : 235);
+    c->deep_build = deep_build;
     c->deep_balance = (int)env_long("IBLB_DEEP_BALANCE", 1);
     c->band_on = (int)env_long("IBLB_IB_BAND", 1);
     c->band_merge = (int)env_long("IBLB_BAND_MERGE", 1);
-#ifdef IBLB_TIMING_PROBES
-    // timing probes that skip work (WRONG results): only in a build made for them
-    c->probe_level = (int)env_long("IBLB_PROBE_LEVEL", 0);
-#else
-    if (env_long("IBLB_PROBE_LEVEL", 0) != 0)
-        std::fprintf(stderr, "iblb: IBLB_PROBE_LEVEL ignored: the library was built without IBLB_TIMING_PROBES\n");
-#endif
     // the device waits' bound (ctx_step.hip:set_wait_ticks; iblb_set_wait_timeout overrides)
     if (const char* w = std::getenv("IBLB_WAIT_TIMEOUT_S")) {
         const double s = std::strtod(w, nullptr);
         if (s > 0.) c->wait_timeout_s = s;
     }
-    c->band_deep_variant = (int)env_long("IBLB_BAND_DEEP_VARIANT", -1);
-    c->wrap_split = (int)env_long("IBLB_WRAP_SPLIT", 1);
     c->band_par_env = (int)env_long("IBLB_BAND_PAR", 1);
     c->band_vhalf_env = (int)env_long("IBLB_BAND_VHALF", 1);
     // cells per lane in a group slab's deep sweeps: f64 two (the wall split needs them: self ring

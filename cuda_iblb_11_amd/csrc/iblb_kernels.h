@@ -49,7 +49,6 @@ struct FusedArgs {
     double* Q;
     Coef c;
     KConst k;           // collide constants folded on the host (iblb_device.h)
-    int variant;        // kernel variant (MODE bits of lbm_kernels.hip), 0 = default
     // IB band patches (band cycle, rows restricted): with row_tab set, cols holds 5 ints per entry
     // from col_begin on, {column, first chunk, end chunk, first row, end row}, and launch entry e
     // covers chunks [first, end) of its column (nchl waves per entry, the extra ones exit).  Q is
@@ -85,9 +84,6 @@ struct FusedArgs {
     // waves share one: a flag left set over zeroed force takes the forced collide with force 0, bit
     // for bit the unforced one; a merged level's fdclr values are still cleared, their flag kept)
     int vhalf = 0;
-    int probe = 0;  // timing probe IBLB_PROBE_LEVEL (WRONG results): 1 point groups skipped, 2 entry waves skipped,
-                    // 3 point groups end after their region, 4 before their spread (5 / 6, the spread
-                    // with plain stores / without chunk flags: round 5, profiles/r05/probe, removed)
 };
 
 // Two iterations per launch (lbm_sweep.hip): g^t -> g^{t+2}, no IB force owed in between.
@@ -98,6 +94,14 @@ struct SkipBox {
     int x0, x1, y0, y1;
 };
 constexpr int MAX_SKIP = 96;
+
+// The deep sweep's build features (lbm_sweep_impl.h:launch_sweepk_vs picks the kernel build from them;
+// one that does not apply to a (type, cells per lane, layout) combination is ignored)
+struct DeepBuild {
+    bool split;   // the wall-row chunks as their own sweep family (one cell per lane), the inner chunks preshifted
+    bool pack;    // f32, two cells per lane: both cells' collides as one packed f32x2 computation
+    bool window;  // two cells per lane, split: the moving populations wait in an LDS window
+};
 
 template <typename T>
 struct Sweep2Args {
@@ -111,7 +115,7 @@ struct Sweep2Args {
     int W;               // output columns per sweep (wave)
     int vs;              // cells per lane; rows, col and plane multiples of vs
     int nch;             // set by launch_sweep2
-    int variant;         // deep sweeps: bit 0 nontemporal stores, bit 1 the f32 wall split
+    DeepBuild build;     // deep sweeps: the build's features
     int nsweep_w = 0;    // wall split (set by the launcher): sweeps of each wall chunk,
     int wall_ch0 = 0;    // inner chunks between the wall chunks,
     int wall_top = 0;    // and the first row of the top wall chunk
@@ -139,7 +143,6 @@ struct Sweep2Args {
     unsigned* done_cnt = nullptr;
     int* edge_waves = nullptr;  // host pointer, written by launch_sweepk (not read on the device)
     int* kinfo = nullptr;       // host pointer: {MODE, VS, resident waves per SIMD, VGPRs} of the build launched
-    int edge_trim = 0;          // balanced sweeps: the first and last sweep this many columns narrower
     int nskip = 0;       // > 0: the patch output regions below are left to the band's last level,
     SkipBox skip[MAX_SKIP];  // sorted by x0, disjoint in columns (a lone slab's deep sweep, a group slab's interior and boundary sweeps)
 };
@@ -164,7 +167,7 @@ hipError_t launch_seq_signal(unsigned* p, unsigned v, hipStream_t s);
 hipError_t launch_test_hold(const unsigned* word, unsigned long long ticks, hipStream_t s);
 // Resident waves per CU of a deep-sweep configuration; *nch = its row chunks for ny rows.
 template <typename T>
-int sweepk_geometry(int depth, int vs, int variant, bool ghost, int ny, int* nch);
+int sweepk_geometry(int depth, int vs, bool ghost, int ny, int* nch);
 
 // Launch geometry of the collide-stream kernel: one wave per (column, 64*V-row chunk).
 inline int chunks_per_column(int ny, int V) { return (ny + 64 * V - 1) / (64 * V); }

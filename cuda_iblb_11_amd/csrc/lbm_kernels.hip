@@ -176,7 +176,6 @@ __global__ __launch_bounds__(256) void band_level_kernel(FusedArgs<T> a) {
     const int ngroups = a.nns > 0 ? a.nns + max(0, a.whi - a.wlo) : 0;
     const int pw = (ngroups * NEXT_LANES + 63) / 64;
     if (gw < pw) {
-        if (a.probe == 1) return;
         const long t = (long)gw * 64 + lane;
         const int gi = (int)(t / NEXT_LANES), n = (int)(t % NEXT_LANES);
         // group gi < nns: point gi (image 0 only when it lies in [wlo, whi)); then one group per point
@@ -189,7 +188,7 @@ __global__ __launch_bounds__(256) void band_level_kernel(FusedArgs<T> a) {
     }
     const int w = gw - pw, ew = a.ncols * a.nchl;
     if (w < ew) {
-        if (a.probe != 2) fused_wave<T, VW, true, MODE>(a, w, lane);
+        fused_wave<T, VW, true, MODE>(a, w, lane);
         return;
     }
     if (w < ew + a.clr_waves) {
@@ -253,16 +252,10 @@ hipError_t launch_fused(const FusedArgs<T>& a, hipStream_t s, hipEvent_t stop) {
     if (waves <= 0) return hipSuccess;
     if (a.row_tab && (a.nns > 0 || a.clr_waves > 0) && !a.flags) return hipErrorInvalidValue;
     const unsigned blocks = (unsigned)((waves + 3) / 4);
-    switch (a.variant) {
-        case 1: return launch_fused_mode<T, 1>(a, blocks, s, stop);
-        case 2: return launch_fused_mode<T, 2>(a, blocks, s, stop);
-        case 3: return launch_fused_mode<T, 3>(a, blocks, s, stop);
-        case 4: return launch_fused_mode<T, 4>(a, blocks, s, stop);
-        case 5: return launch_fused_mode<T, 5>(a, blocks, s, stop);
-        case 6: return launch_fused_mode<T, 6>(a, blocks, s, stop);
-        case 7: return launch_fused_mode<T, 7>(a, blocks, s, stop);
-        default: return launch_fused_mode<T, 0>(a, blocks, s, stop);
-    }
+    // the measured build of each precision: f64 the DPP row shift with nontemporal stores,
+    // f32 nontemporal loads and stores
+    constexpr int MODE = sizeof(T) == 8 ? (MODE_NT_STORE | MODE_SHIFT) : (MODE_NT_STORE | MODE_NT_LOAD);
+    return launch_fused_mode<T, MODE>(a, blocks, s, stop);
 }
 
 // ---- boot step: collide f^0 with given rho^0, u^0, force^0 (main.cu:720-754, it = 0) --

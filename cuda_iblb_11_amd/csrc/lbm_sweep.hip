@@ -7,7 +7,7 @@ namespace iblb {
 // the K-iteration kernels are built in lbm_sweepk<K>.hip
 #define IBLB_SWEEPK_EXTERN(T, K, S)                                                          \
     extern template hipError_t launch_sweepk_depth<T, K, S>(const Sweep2Args<T>&, hipStream_t, hipEvent_t, hipEvent_t); \
-    extern template int deep_geometry<T, K, S>(int, int, int, int*);
+    extern template int deep_geometry<T, K, S>(int, int, int*);
 #define IBLB_SWEEPK_EXTERN_K(K)                                                                               \
     IBLB_SWEEPK_EXTERN(double, K, false) IBLB_SWEEPK_EXTERN(double, K, true) IBLB_SWEEPK_EXTERN(float, K, false) \
     IBLB_SWEEPK_EXTERN(float, K, true)
@@ -30,20 +30,20 @@ static hipError_t launch_sweepk_slab(const Sweep2Args<T>& a, int depth, hipStrea
 
 
 template <typename T>
-int sweepk_geometry(int depth, int vs, int variant, bool slab, int ny, int* nch) {
+int sweepk_geometry(int depth, int vs, bool slab, int ny, int* nch) {
     *nch = 0;
     if (vs != 1 && vs != 2) return 0;
     switch (depth) {
-        case 3: return slab ? deep_geometry<T, 3, true>(vs, variant, ny, nch) : deep_geometry<T, 3, false>(vs, variant, ny, nch);
-        case 4: return slab ? deep_geometry<T, 4, true>(vs, variant, ny, nch) : deep_geometry<T, 4, false>(vs, variant, ny, nch);
-        case 5: return slab ? deep_geometry<T, 5, true>(vs, variant, ny, nch) : deep_geometry<T, 5, false>(vs, variant, ny, nch);
-        case 6: return slab ? deep_geometry<T, 6, true>(vs, variant, ny, nch) : deep_geometry<T, 6, false>(vs, variant, ny, nch);
-        case 7: return slab ? deep_geometry<T, 7, true>(vs, variant, ny, nch) : deep_geometry<T, 7, false>(vs, variant, ny, nch);
+        case 3: return slab ? deep_geometry<T, 3, true>(vs, ny, nch) : deep_geometry<T, 3, false>(vs, ny, nch);
+        case 4: return slab ? deep_geometry<T, 4, true>(vs, ny, nch) : deep_geometry<T, 4, false>(vs, ny, nch);
+        case 5: return slab ? deep_geometry<T, 5, true>(vs, ny, nch) : deep_geometry<T, 5, false>(vs, ny, nch);
+        case 6: return slab ? deep_geometry<T, 6, true>(vs, ny, nch) : deep_geometry<T, 6, false>(vs, ny, nch);
+        case 7: return slab ? deep_geometry<T, 7, true>(vs, ny, nch) : deep_geometry<T, 7, false>(vs, ny, nch);
         default: return 0;
     }
 }
-template int sweepk_geometry<double>(int, int, int, bool, int, int*);
-template int sweepk_geometry<float>(int, int, int, bool, int, int*);
+template int sweepk_geometry<double>(int, int, bool, int, int*);
+template int sweepk_geometry<float>(int, int, bool, int, int*);
 
 template <typename T>
 hipError_t launch_sweepk(Sweep2Args<T> a, int depth, bool slab, hipStream_t s, hipEvent_t stop, hipEvent_t start) {

@@ -39,9 +39,6 @@ namespace iblb {
 
 // sweep only (MODE bits 1, 2 as in lbm_vec.h): no software prefetch of the next column (two-step
 // sweeps); the deep sweep's wall split (sweepk_kernel)
-#ifndef IBLB_WALK_UL
-#define IBLB_WALK_UL 1  // the LDS-window walks load the next column unconditionally (0: round 6's A/B base)
-#endif
 enum { MODE_NO_PREFETCH = 8, MODE_SPLIT = 16, MODE_PACK = 64, MODE_SKIP = 128, MODE_PRESHIFT = 256, MODE_LDSWIN = 512,
        MODE_WT_STORE = 1024 };
 
@@ -924,9 +921,8 @@ __device__ __forceinline__ double sweepk_walk(const Sweep2Args<T>& a, int xa, in
     // renaming: the compiler kept the windows in AGPRs, 1399 instructions per f64 step against 1392)
     constexpr bool LW = lds_window<T, VS, MODE, WL>();
     for (int i = 0; i < nl1; ++i)
-        sweepk_iter<T, VS, MODE, K, SLAB, REV, LW, LW && IBLB_WALK_UL>(a, i, nl1, x0, xa, xb, row0, off, lane, r0, et, owner,
-                                                                    bot, top, walls, WA, WB, cur, q, bo, rc, fin, fi, fown,
-                                                                    sp, lw, cp);
+        sweepk_iter<T, VS, MODE, K, SLAB, REV, LW, LW>(a, i, nl1, x0, xa, xb, row0, off, lane, r0, et, owner, bot, top, walls,
+                                                       WA, WB, cur, q, bo, rc, fin, fi, fown, sp, lw, cp);
     return q;
 }
 
@@ -1003,15 +999,11 @@ __device__ __forceinline__ void edge_done(unsigned* cnt, bool wt) {
     if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// Balanced sweep s of nsw over [cb, ce): floor/ceil((ce - cb) / nsw) columns; trim > 0 makes the first
-// and last sweeps `trim` columns narrower (a slab interior's edge waves, which also wait and signal)
-__host__ __device__ inline void balanced_range(int cb, int ce, int trim, int s, int nsw, int& xa, int& xb) {
-    const long n = (long)(ce - cb) + 2L * trim;
-    xa = cb - trim + (int)(s * n / nsw);
-    xb = cb - trim + (int)((s + 1) * n / nsw);
-    xa = xa < cb ? cb : xa;
-    xb = xb > ce ? ce : xb;
-    xb = xb < xa ? xa : xb;  // (the launcher keeps trim below every sweep's share: never empty there)
+// Balanced sweep s of nsw over [cb, ce): floor/ceil((ce - cb) / nsw) columns
+__host__ __device__ inline void balanced_range(int cb, int ce, int s, int nsw, int& xa, int& xb) {
+    const long n = (long)(ce - cb);
+    xa = cb + (int)(s * n / nsw);
+    xb = cb + (int)((s + 1) * n / nsw);
 }
 
 // G ghost lanes at each wave edge (G * VS >= K - 1 rows)
@@ -1044,7 +1036,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
         xa = a.col_begin + sw * a.col_step;
         xb = min(xa + a.W, a.col_end);
     } else {  // balanced: nsw sweeps of floor/ceil((col_end - col_begin) / nsw) columns
-        balanced_range(a.col_begin, a.col_end, a.edge_trim, sw, nsw, xa, xb);
+        balanced_range(a.col_begin, a.col_end, sw, nsw, xa, xb);
     }
     const bool edge = SLAB && (xa < a.wait_lo || xb > a.wait_hi);
     // an edge wave that signals its stores: write-through in the wall-split walks (the slab builds)
@@ -1188,12 +1180,6 @@ static hipError_t launch_sweepk_mode(Sweep2Args<T> b, hipStream_t s, hipEvent_t 
     } else {
         waves = (long)b.nsweep * b.nch;
     }
-    if (b.col_step <= 0 && b.edge_trim > 0) {
-        // the first and last sweeps keep at least one column: trim < every sweep's share
-        const long n = b.col_end - b.col_begin;
-        const long nsw = std::max((long)b.nsweep, (MODE & MODE_SPLIT) ? (long)b.nsweep_w : 0L);
-        b.edge_trim = (int)std::min((long)b.edge_trim, std::max(0L, n / std::max(1L, nsw) - 1));
-    }
     if (b.edge_waves) {  // the waves that will add to done_cnt (sweepk_kernel's `edge`)
         auto edges = [&](int nsw) {
             int e = 0;
@@ -1203,7 +1189,7 @@ static hipError_t launch_sweepk_mode(Sweep2Args<T> b, hipStream_t s, hipEvent_t 
                     xa = b.col_begin + sw * b.col_step;
                     xb = std::min(xa + b.W, b.col_end);
                 } else {
-                    balanced_range(b.col_begin, b.col_end, b.edge_trim, sw, nsw, xa, xb);
+                    balanced_range(b.col_begin, b.col_end, sw, nsw, xa, xb);
                 }
                 e += (xa < b.wait_lo || xb > b.wait_hi) ? 1 : 0;
             }
@@ -1234,72 +1220,57 @@ static hipError_t launch_sweepk_mode(Sweep2Args<T> b, hipStream_t s, hipEvent_t 
     return hipGetLastError();
 }
 
-// the wall split (variant bit 1): two cells per lane in the inner chunks; f32 at three waves per
-// SIMD, f64 at one
-template <typename T, int VS>
-constexpr bool wall_split_built() { return VS == 2 || VS == 1; }
-
+// The build of one (type, cells per lane, depth, layout) for the features asked (DeepBuild); a feature
+// that does not apply here is ignored.  MODE bit 0 (nontemporal stores) is in every build.
 template <typename T, int VS, int K, bool SLAB>
 static hipError_t launch_sweepk_vs(const Sweep2Args<T>& a, hipStream_t s, hipEvent_t stop, hipEvent_t start) {
     constexpr int G = ghost_lanes<K, VS>();
     const int rows_per_wave = (64 - 2 * G) * VS;  // owned rows
+    constexpr bool F32 = sizeof(T) == 4;
     Sweep2Args<T> b = a;
     b.nch = (a.L.ny + rows_per_wave - 1) / rows_per_wave;
-    if constexpr (wall_split_built<T, VS>()) {
-        // rows: [0, OWN1) bottom wall chunk, inner chunks of rows_per_wave, top wall chunk from an even
-        // row (two-cell lanes of the inner chunks never straddle it) holding the last OWN1 or fewer rows
+    // The wall split: two cells per lane in the inner chunks, and f32 with one (a group slab).  Rows:
+    // [0, OWN1) bottom wall chunk, inner chunks of rows_per_wave, top wall chunk from an even row (two-cell
+    // lanes of the inner chunks never straddle it) holding the last OWN1 or fewer rows
+    if constexpr (VS == 2 || F32) {
         constexpr int OWN1 = 64 - 2 * ghost_lanes<K, 1>();
         const int top = (a.L.ny - OWN1 + 1) & ~1;
         // f32, one cell per lane (a group slab's band cycle): the split with the skip regions too
-        constexpr bool SPLIT_SKIP = sizeof(T) == 4 && VS == 1 && !SLAB;
-        if ((a.variant & 2) && (VS == 2 || (a.variant & 64)) && (a.nskip == 0 || SPLIT_SKIP) && top > OWN1) {
+        constexpr bool SPLIT_SKIP = F32 && VS == 1 && !SLAB;
+        if (a.build.split && (a.nskip == 0 || SPLIT_SKIP) && top > OWN1) {
             b.wall_top = top;
             b.wall_ch0 = (top - OWN1 + rows_per_wave - 1) / rows_per_wave;
-            if constexpr (SPLIT_SKIP) {
-                constexpr int WPE = 3;  // (four waves: 6 dwords of scratch spills)
-                if (a.nskip > 0) {
-                    if (a.variant & 32)
-                        return launch_sweepk_mode<T, VS, 1 | MODE_SPLIT | MODE_PRESHIFT | MODE_SKIP, K, SLAB, WPE>(b, s, stop,
-                                                                                                         start);
-                    return launch_sweepk_mode<T, VS, 1 | MODE_SPLIT | MODE_SKIP, K, SLAB, WPE>(b, s, stop, start);
-                }
-            }
-            // bit 3: the inner chunks packed, two waves per SIMD (the packed inner walk needs 191 VGPRs;
-            // forced to three waves it spills 21 dwords: 0.417 vs 0.323 ms per M f32 launch, profiles/r04/pack)
-            constexpr int WPE = sizeof(T) == 4 ? (VS == 2 ? 3 : 4) : (VS == 2 ? 1 : 2);
-            if constexpr (sizeof(T) == 4 && VS == 2)
-                if (a.variant & 8) {
-                    // bit 7 (round 5): two of the three moving populations in LDS, three waves per SIMD
+            if constexpr (SPLIT_SKIP)  // three waves per SIMD (four: 6 dwords of scratch spills)
+                if (a.nskip > 0)
+                    return launch_sweepk_mode<T, VS, 1 | MODE_SPLIT | MODE_PRESHIFT | MODE_SKIP, K, SLAB, 3>(b, s, stop, start);
+            if constexpr (F32 && VS == 2)
+                if (a.build.pack) {
+                    // the window (round 5): two of the three moving populations in LDS, three waves per SIMD
                     if constexpr (!SLAB)
-                        if (a.variant & 128)
+                        if (a.build.window)
                             return launch_sweepk_mode<T, VS, 1 | MODE_SPLIT | MODE_PACK | MODE_LDSWIN, K, SLAB, 3>(b, s, stop,
                                                                                                          start);
+                    // the inner chunks packed, two waves per SIMD (the packed inner walk needs 191 VGPRs; forced
+                    // to three waves it spills 21 dwords: 0.417 vs 0.323 ms per M f32 launch, profiles/r04/pack)
                     return launch_sweepk_mode<T, VS, 1 | MODE_SPLIT | MODE_PACK, K, SLAB, 2>(b, s, stop, start);
                 }
-            // bit 7 (f64, two cells per lane, with bit 5): the LDS window of the inner chunks
-            if constexpr (sizeof(T) == 8 && VS == 2)
-                if ((a.variant & 160) == 160)
+            // waves per SIMD: f32 three at two cells per lane, four at one; f64 one
+            constexpr int WPE = F32 ? (VS == 2 ? 3 : 4) : 1;
+            if constexpr (!F32)  // (VS == 2) the LDS window of the inner chunks
+                if (a.build.window)
                     return launch_sweepk_mode<T, VS, 1 | MODE_SPLIT | MODE_PRESHIFT | MODE_LDSWIN, K, SLAB, WPE>(b, s, stop,
                                                                                                            start);
-            if (a.variant & 32)
-                return launch_sweepk_mode<T, VS, 1 | MODE_SPLIT | MODE_PRESHIFT, K, SLAB, WPE>(b, s, stop, start);
-            if (a.variant & 1) return launch_sweepk_mode<T, VS, 1 | MODE_SPLIT, K, SLAB, WPE>(b, s, stop, start);
-            return launch_sweepk_mode<T, VS, MODE_SPLIT, K, SLAB, WPE>(b, s, stop, start);
+            return launch_sweepk_mode<T, VS, 1 | MODE_SPLIT | MODE_PRESHIFT, K, SLAB, WPE>(b, s, stop, start);
         }
     }
     // the IB band cycle's deep and boundary sweeps beside its last level: patch output rows left out
     if (a.nskip > 0) return launch_sweepk_mode<T, VS, 1 | MODE_SKIP, K, SLAB, 1>(b, s, stop, start);
-    // variants: bit 0 = nontemporal stores (default), 0 = plain; bit 3 (f32, two cells per lane): the
-    // packed collide (both cells in one f32x2 computation, relax_dev)
-    if constexpr (sizeof(T) == 4 && VS == 2)
-        if (a.variant & 8) return launch_sweepk_mode<T, VS, 1 | MODE_PACK, K, SLAB, 1>(b, s, stop, start);
-    // bit 5 without bit 1: level 1 loads each plane at its pull's rows (no wave-edge loads, no lane
-    // shift) in every chunk.  Slower than the plain walk (M f64 0.559 vs 0.521 ms per launch,
-    // profiles/r04/split64): the wall waves, which set the launch time here, wait on the wall rows'
-    // uniform loads.  With bit 1 (the split) the inner chunks take it and the wall waves have slack.
-    if ((a.variant & 34) == 32) return launch_sweepk_mode<T, VS, 1 | MODE_PRESHIFT, K, SLAB, 1>(b, s, stop, start);
-    if (a.variant & 1) return launch_sweepk_mode<T, VS, 1, K, SLAB, 1>(b, s, stop, start);
-    return launch_sweepk_mode<T, VS, 0, K, SLAB, 1>(b, s, stop, start);
+    if constexpr (F32 && VS == 2)
+        if (a.build.pack) return launch_sweepk_mode<T, VS, 1 | MODE_PACK, K, SLAB, 1>(b, s, stop, start);
+    // (the preshift in every chunk, without the split, is slower than this plain walk: M f64 0.559 vs 0.521 ms
+    // per launch, profiles/r04/split64: the wall waves, which set the launch time, wait on the wall rows'
+    // uniform loads; with the split the inner chunks take it and the wall waves have slack)
+    return launch_sweepk_mode<T, VS, 1, K, SLAB, 1>(b, s, stop, start);
 }
 
 // cells per lane: 2 or 1 (4 in f32 measured slower: one wave per SIMD, profiles/r01d4_*)
@@ -1314,13 +1285,13 @@ hipError_t launch_sweepk_depth(const Sweep2Args<T>& a, hipStream_t s, hipEvent_t
 // resident waves per CU and waves per launch column-chunk geometry of one configuration (the
 // context sizes the CUs it reserves for the boundary sweeps with it)
 template <typename T, int K, bool SLAB>
-int deep_geometry(int vs, int variant, int ny, int* nch) {
+int deep_geometry(int vs, int ny, int* nch) {
     if (vs == 2) {
         *nch = (ny + (64 - 2 * ghost_lanes<K, 2>()) * 2 - 1) / ((64 - 2 * ghost_lanes<K, 2>()) * 2);
-        return (int)((variant & 1) ? waves_per_cu<T, 2, 1, K, SLAB, 1>() : waves_per_cu<T, 2, 0, K, SLAB, 1>());
+        return (int)waves_per_cu<T, 2, 1, K, SLAB, 1>();
     }
     *nch = (ny + (64 - 2 * ghost_lanes<K, 1>()) - 1) / (64 - 2 * ghost_lanes<K, 1>());
-    return (int)((variant & 1) ? waves_per_cu<T, 1, 1, K, SLAB, 1>() : waves_per_cu<T, 1, 0, K, SLAB, 1>());
+    return (int)waves_per_cu<T, 1, 1, K, SLAB, 1>();
 }
 
 }  // namespace iblb

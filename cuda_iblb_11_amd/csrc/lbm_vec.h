@@ -35,7 +35,8 @@ struct Calc { typedef double R; };
 template <>
 struct Calc<float> { typedef float R; };
 
-// Kernel variants (MODE bits), selected per context for A/B measurement:
+// Kernel build features (MODE bits); the one-step kernel is built once per precision (launch_fused:
+// f64 NT_STORE | SHIFT, f32 NT_STORE | NT_LOAD), the sweeps add bits of their own (lbm_sweep_impl.h):
 //   MODE_NT_STORE  populations written with nontemporal stores
 //   MODE_NT_LOAD   populations read with nontemporal loads (each element is read once)
 //   MODE_SHIFT     all planes loaded 16-B aligned; the +-1-row shift of the c_y != 0 planes

@@ -77,26 +77,16 @@ def test_channel_shapes(gpu, oracle, shape):
 
 
 @pytest.mark.parametrize("precision", ["f64", "f32"])
-def test_fused_variants_bit_identical(gpu, oracle, precision, monkeypatch):
-    """Every collide-stream variant (misaligned loads vs DPP row shift, temporal vs
-    nontemporal) moves the same values: results must be bit-identical, on shapes whose
-    column height is not a multiple of the wave chunk and with several chunks per column."""
-    from cuda_iblb_11_amd import workloads as W
+def test_fused_ragged_shapes_match_oracle(gpu, oracle, precision):
+    """The one-step kernel's one build per precision (f64: DPP row shift, nontemporal stores; f32:
+    nontemporal loads and stores) against the oracle over 30 steps, on shapes whose column height is
+    not a multiple of the wave chunk, with several chunks per column, and with a single chunk."""
     for nx, ny in [(37, 300), (5, 1100), (2, 63)]:
-        rho, u = W.perturbed_state(nx, ny, 4)
-        outs = []
-        for v in range(8):
-            monkeypatch.setenv("IBLB_FUSED_VARIANT", str(v))
-            lat = gpu.Lattice(nx, ny, W.TAU, W.TAU2, precision=precision, body_force=(1e-6, 3e-7))
-            lat.set_state(rho, u)
-            lat.step(30)
-            outs.append(lat.populations())
+        lat, sim = run_pair(gpu, oracle, nx, ny, 30, precision=precision)
+        try:
+            check_fields(lat, sim, TIGHT if precision == "f64" else TOL32)
+        finally:
             lat.close()
-        for v in range(1, 8):
-            assert np.array_equal(outs[v], outs[0]), (nx, ny, v)
-    monkeypatch.delenv("IBLB_FUSED_VARIANT")
-    lat, sim = run_pair(gpu, oracle, 37, 300, 30, precision=precision)
-    check_fields(lat, sim, TIGHT if precision == "f64" else TOL32)
 
 
 def test_boot_step_and_initial_state(gpu, oracle):
@@ -284,6 +274,20 @@ def test_errors_are_loud(gpu):
     slab.set_state()
     with pytest.raises(gpu.IblbError):
         slab.step(1)  # slab not linked to neighbours
+
+
+def test_deep_build_knob_takes_its_words_only(gpu, monkeypatch):
+    """IBLB_DEEP_BUILD is a comma list of split, pack, window, or the word plain: anything else makes
+    iblb_create fail with IBLB_ERR_ARG and a message naming the knob."""
+    from cuda_iblb_11_amd import workloads as W
+    for bad in ("163", "", "split,,pack", "plain,split", "Split"):
+        monkeypatch.setenv("IBLB_DEEP_BUILD", bad)
+        with pytest.raises(gpu.IblbError) as e:
+            gpu.Lattice(16, 8, W.TAU, W.TAU2)
+        assert e.value.code == gpu.IBLB_ERR_ARG and "IBLB_DEEP_BUILD" in str(e.value), (bad, str(e.value))
+    for good in ("plain", "window,split", "split,pack,window"):
+        monkeypatch.setenv("IBLB_DEEP_BUILD", good)
+        gpu.Lattice(16, 8, W.TAU, W.TAU2).close()
 
 
 @pytest.mark.parametrize("n,with_ib,precision,overlap,bulk,depth",
@@ -620,10 +624,11 @@ def test_sweep_deep_bit_identical(gpu, oracle, precision, depth, monkeypatch):
     """K = 3 or 4 iterations per launch (IBLB_SWEEP_DEPTH=K, lone slab: K-1 register windows,
     the chunk-edge ghost rows shrinking by one per level, ceil((K-1)/VS) ghost lanes per edge)
     equal one-step launches bit for bit, for every cells-per-lane width, sweep length (fixed
-    and balanced to whole rounds of waves), variant (f32 variants 2, 3: the wall-row chunks as
-    their own sweep family of the three-wave build; 8, 9, 11: the packed two-cell collide, 11 with
-    the wall chunks split off; 163: f64 LDS window; 139: f32 packed split with two of the three moving
-    populations in LDS, three waves per SIMD), wave order and walking direction, on
+    and balanced to whole rounds of waves), build (IBLB_DEEP_BUILD; split: the wall-row chunks as
+    their own sweep family, the inner chunks preshifted; pack: the f32 packed two-cell collide, alone
+    and with the wall chunks split off; window: the LDS window, f64 with the split, f32 with the packed
+    split: two of the three moving populations in LDS, three waves per SIMD; a feature that does not
+    apply to a precision or cells-per-lane width is ignored), wave order and walking direction, on
     ragged shapes including fewer columns than the K-column reach (periodic images wrap more
     than once).  Calls of 1 + 10K, 2 and 2K - 1 iterations: boot + 10 deep launches, one
     two-iteration launch, then (K >= 4) one launch of depth K - 1 and one of depth K (a call mixes
@@ -645,13 +650,16 @@ def test_sweep_deep_bit_identical(gpu, oracle, precision, depth, monkeypatch):
         monkeypatch.setenv("IBLB_SWEEP", "1")
         monkeypatch.setenv("IBLB_SWEEP_DEPTH", str(depth))
         for vs in vss:
-            for w, var, bal in [(4, 1, 0), (1, 0, 0), (3, 1, 1), (32, 1, 0), (7, 0, 1), (48, 1, 1), (5, 3, 1), (48, 2, 1),
-                                (5, 9, 1), (6, 8, 0), (48, 11, 1), (5, 11, 1), (5, 33, 1), (48, 33, 0), (5, 35, 1), (7, 99, 1), (5, 67, 1),
-                                (6, 35, 0), (4, 11, 0), (3, 3, 0), (5, 107, 1), (6, 107, 0), (5, 163, 1), (48, 163, 0),
-                                (5, 139, 1), (48, 139, 0), (6, 235, 1)]:
+            for w, var, bal in [(4, "plain", 0), (1, "plain", 0), (3, "plain", 1), (32, "plain", 0), (7, "plain", 1),
+                                (48, "plain", 1), (5, "plain", 1), (48, "plain", 0),
+                                (5, "split", 1), (48, "split", 1), (7, "split", 1), (6, "split", 0), (3, "split", 0),
+                                (5, "pack", 1), (6, "pack", 0),
+                                (48, "split,pack", 1), (5, "split,pack", 1), (4, "split,pack", 0), (6, "split,pack", 0),
+                                (5, "split,window", 1), (48, "split,window", 0),
+                                (5, "split,pack,window", 1), (48, "split,pack,window", 0), (6, "split,pack,window", 1)]:
                 monkeypatch.setenv("IBLB_DEEP_VS", str(vs))
                 monkeypatch.setenv("IBLB_DEEP_W", str(w))
-                monkeypatch.setenv("IBLB_DEEP_VARIANT", str(var))
+                monkeypatch.setenv("IBLB_DEEP_BUILD", var)
                 monkeypatch.setenv("IBLB_DEEP_BALANCE", str(bal))
                 lat = gpu.Lattice(nx, ny, W.TAU, W.TAU2, precision=precision, body_force=(1e-6, 3e-7))
                 lat.set_state(rho, u)
@@ -666,20 +674,36 @@ def test_sweep_deep_bit_identical(gpu, oracle, precision, depth, monkeypatch):
                                                   float(np.max(np.abs(f - f_ref))))
                 assert abs(lat.flux - q_ref) <= 1e-12 * abs(q_ref), (lat.flux, q_ref)
                 lat.close()
-    for name in ("IBLB_SWEEP_DEPTH", "IBLB_DEEP_VS", "IBLB_DEEP_W", "IBLB_DEEP_VARIANT", "IBLB_DEEP_BALANCE"):
+    for name in ("IBLB_SWEEP_DEPTH", "IBLB_DEEP_VS", "IBLB_DEEP_W", "IBLB_DEEP_BUILD", "IBLB_DEEP_BALANCE"):
         monkeypatch.delenv(name)
+
+
+def _deep_build(lat):
+    tm = lat.timing()
+    return tm["deep_mode"], tm["deep_vs"], tm["deep_waves_per_simd"], tm["deep_vgprs"]
 
 
 @pytest.mark.parametrize("precision", ["f64", "f32"])
 def test_default_deep_builds(gpu, precision, monkeypatch):
-    """With no IBLB_* variable in the environment a lone slab's depth-7 sweep runs the measured build,
-    (MODE, cells per lane, waves per SIMD) of iblb_timing: the wall split with the LDS window on 300
-    rows (f64 with the preshift at one wave, f32 packed at three); on 63 rows, fewer than two wall
-    chunks hold, the unsplit walk (f32: packed)."""
+    """With no IBLB_* variable in the environment (but the one that names the role) every role the
+    library selects a depth-7 build for runs the measured one: (MODE, cells per lane, waves per SIMD,
+    VGPRs) of iblb_timing, read from the tree before the variant masks were retired; exact, these
+    name which kernel ran and how it was compiled.
+    Lone slab: the wall split with the LDS window on 300 rows (f64 with the preshift at one wave, f32
+    packed at three); on 63 rows, fewer than two wall chunks hold, the unsplit walk (f32: packed).
+    RCCL self-ring slab (256 x 512): f64 the same build with ghost columns, f32 the one-cell split.
+    A lone slab's band cycle (256 x 160, two point lines): behind the chain (IBLB_BAND_PAR=0) f64 the
+    split without the window, f32 the plain walk; beside the last level (2) the skip-region walk.
+    The self-ring band cycle in f32: the one-cell split with the skip regions."""
     from cuda_iblb_11_amd import workloads as W
-    for name in [n for n in os.environ if n.startswith("IBLB_")]:
-        monkeypatch.delenv(name)
-    want = {"f64": {300: (785, 2, 1), 63: (1, 2, 1)}, "f32": {300: (593, 2, 3), 63: (65, 2, 1)}}[precision]
+    def clear(**env):
+        for name in [n for n in os.environ if n.startswith("IBLB_")]:
+            monkeypatch.delenv(name)
+        for k, v in env.items():
+            monkeypatch.setenv(k, str(v))
+    clear()
+    want = {"f64": {300: (785, 2, 1, 241), 63: (1, 2, 1, 442)},
+            "f32": {300: (593, 2, 3, 161), 63: (65, 2, 1, 324)}}[precision]
     for ny in (300, 63):
         rho, u = W.perturbed_state(37, ny, 7)
         lat = gpu.Lattice(37, ny, W.TAU, W.TAU2, precision=precision)
@@ -688,7 +712,60 @@ def test_default_deep_builds(gpu, precision, monkeypatch):
             lat.step(1 + 7)
             tm = lat.timing()
             assert tm["deep_launches"] == 1 and tm["deep_iterations"] == 7, tm
-            assert (tm["deep_mode"], tm["deep_vs"], tm["deep_waves_per_simd"]) == want[ny], (ny, tm)
+            assert _deep_build(lat) == want[ny], (ny, tm)
+        finally:
+            lat.close()
+
+    # the RCCL self ring's slab: the interior sweep of one deep cycle
+    clear(IBLB_RCCL_SELF=1)
+    rho, u = W.perturbed_state(256, 512, 41)
+    lat = gpu.Lattice(256, 512, W.TAU, W.TAU2, precision=precision, body_force=(1e-6, 2e-7))
+    try:
+        lat.set_state(rho, u)
+        lat.attach_rccl(gpu.rccl_unique_id(), 1, 0)
+        lat.step(1)
+        lat.step(7)
+        assert lat.timing()["deep_launches"] == 1, lat.timing()
+        assert _deep_build(lat) == {"f64": (785, 2, 1, 243), "f32": (273, 1, 4, 128)}[precision], lat.timing()
+    finally:
+        lat.close()
+
+    # a lone slab's band cycle: its deep sweep behind the chain (0) and beside the last level (2)
+    want = {"f64": {0: (273, 2, 1, 398), 2: (129, 2, 1, 450)},
+            "f32": {0: (1, 2, 2, 228), 2: (129, 2, 2, 234)}}[precision]
+    a, b = _line(64.37, 60), _line(171.6, 48, y0=20.0)
+    pts = tuple(np.concatenate([p, q]) for p, q in zip(a, b))
+    for par in (0, 2):
+        clear(IBLB_BAND_PAR=par)
+        rho, u = W.perturbed_state(256, 160, 11)
+        lat = gpu.Lattice(256, 160, W.TAU, W.TAU2, precision=precision, body_force=(1e-6, 0.0), max_points=4096)
+        try:
+            lat.set_state(rho, u)
+            lat.set_lagrangian(*pts)
+            lat.step(1 + 7)
+            tm = lat.timing()
+            assert tm["deep_launches"] == 1 and tm["band_cycles"] == 1, tm
+            assert _deep_build(lat) == want[par], (par, tm)
+        finally:
+            lat.close()
+
+    if precision == "f32":  # the self ring's band cycle (moving filaments inside the slab)
+        from test_gpu_bulk import _schedule, _swaying
+        clear(IBLB_RCCL_SELF=1)
+        points = _swaying(256, n_fil=2, pts=40)
+        rho, u = W.perturbed_state(256, 128, 17)
+        lat = gpu.Lattice(256, 128, W.TAU, W.TAU2, precision="f32", body_force=(1e-6, 0.0), max_points=120)
+        try:
+            lat.set_state(rho, u)
+            lat.attach_rccl(gpu.rccl_unique_id(), 1, 0)
+            t = 0
+            for n in (1, 7):
+                lat.set_lagrangian_steps(*_schedule(points, t, n))
+                lat.step(n)
+                t += n
+            tm = lat.timing()
+            assert tm["deep_launches"] == 1 and tm["band_cycles"] == 1, tm
+            assert _deep_build(lat) == (401, 1, 3, 133), tm
         finally:
             lat.close()
 

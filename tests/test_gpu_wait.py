@@ -209,15 +209,10 @@ def test_edge_flag_modes(gpu, monkeypatch, precision, flag):
     ref.close()
 
 
-@pytest.mark.parametrize("trim,variant", [(4, None), (1000, None), (0, 35)])
-def test_edge_trim_and_interior_variant(gpu, monkeypatch, trim, variant):
-    """IBLB_EDGE_TRIM (the interior's first / last sweep narrower; 1000 is clamped so that every sweep
-    keeps a column) and IBLB_INTERIOR_VARIANT (the interior in another deep variant):
-    still bit-identical to the lone slab."""
-    env = {"IBLB_EDGE_TRIM": trim}
-    if variant is not None:
-        env["IBLB_INTERIOR_VARIANT"] = variant
-    _env(monkeypatch, **env)
+def test_slab_chain_default_handoff(gpu, monkeypatch):
+    """The default environment (each precision's own hand-off, no knob set): a boot step, four chained
+    deep cycles and a mixed call, bit-identical to the lone slab in both precisions."""
+    _env(monkeypatch)
     for precision in ("f64", "f32"):
         ref, ring, _, _ = _slab_run(gpu, precision, (1, 4 * K, 2 * K - 1), seed=49)
         ring.close()
