@@ -4,6 +4,7 @@
 //   ctx_step.hip   halo exchange, the one-step / two-step / deep schedules, iblb_step, local and
 //                  RCCL groups, the output gather
 //   ctx_band.hip   the IB band cycle (K iterations per cycle with an owed force every iteration)
+//   band_plan.h    the band cycle's planner: pure host functions (no HIP), checked on the CPU
 //
 // Time-step bookkeeping.  The reference iteration (main.cu:852-909) is
 //   f0,F = equilibrium(u^t, rho^t, force^t); f1 = collision(f^t); f^{t+1} = stream(f1);
@@ -39,6 +40,7 @@
 
 #include "../../include/iblb.h"
 
+#include "band_plan.h"
 #include "cilia_kernels.h"
 #include "iblb_kernels.h"
 
@@ -124,17 +126,12 @@ struct iblb_ctx {
     int band_on = 1;             // IBLB_IB_BAND
     bool band_valid = false;     // the installed plan covers the points of the next cycle
     bool band_dirty = false;     // static points changed (or the context was linked): plan again
-    std::vector<std::array<int, 4>> band_b;  // installed patches {x0, x1, y0, y1} (local columns)
-    int band_d = 0;              // ghost depth the installed trapezoids read (0: all inside the slab)
-    int band_x = 0;              // halo depth of the cycle's exchange (slab groups; same on every rank)
+    iblbh::BandPlan plan;        // the installed plan (band_plan.h): assigned whole, and only with band_valid
     int* band_pin[iblbh::BAND_PIN_SLOTS] = {nullptr, nullptr, nullptr, nullptr};
     size_t band_pin_cap = 0;     // ints per slot
     hipEvent_t band_pin_ev[iblbh::BAND_PIN_SLOTS] = {nullptr, nullptr, nullptr, nullptr};
     int band_pin_i = 0, band_pin_cur = -1;
     int* band_tab = nullptr;     // the installed plan's level tables (a pinned slot)
-    std::vector<int> band_off, band_n, band_nchl;  // level j: first entry, entries, chunks per entry
-    long long band_deep_lu = 0, band_lu = 0;       // cells of the deep sweep / of all trapezoid levels
-    int band_flux = -1, band_fy0 = 0, band_fy1 = 0;  // flux column in a patch output, the patch's rows
     bool band_run = false;       // the last step was a band cycle on band_st / deep_st (not joined)
     long long band_retry_t = 0;  // a declined schedule plan: next attempt at this iteration
     hipEvent_t band_end = nullptr; // recorded on the deep stream at the end of the last band cycle
@@ -142,20 +139,16 @@ struct iblb_ctx {
     void* sbuf[2] = {nullptr, nullptr};
     int band_merge = 1;          // IBLB_BAND_MERGE: 1 auto, 2 always, 0 never: each level's launch also
                                  // evaluates the next level's force (merged chain)
-    bool band_merged = false;    // the installed plan runs the merged chain
     int band_vhalf_env = 1;      // IBLB_BAND_VHALF: f32 chained chain's level launches at half-height waves
-    bool band_vhalf = false;     // the installed plan's level entries are in chunks of 64 * V/2 rows
     double* bf_alloc = nullptr;  // merged chain: two more dense force buffers (levels j % 3 = 1, 2) ...
     uint8_t* bfl_alloc = nullptr;  // ... and their chunk flags, one per 64 * V rows.  Full-height levels clear a flag
-                                   // with the force rows they consume (zero between cycles); f32 half-height levels
-                                   // (band_vhalf) leave the flags set, here and in `flags`, since two waves read each:
+                                   // with the force rows they consume; f32 half-height levels (plan.vhalf) leave
+                                   // the flags set between cycles, here and in `flags`, since two waves read each:
                                    // there only the force rows are zeroed, and a set flag over zero rows is harmless
     double* bfd[2] = {nullptr, nullptr};
     uint8_t* bfl[2] = {nullptr, nullptr};
     int band_par_env = 1;        // IBLB_BAND_PAR: the last level beside the deep sweep (lone and group slabs)
-    bool band_par = false;       // the installed plan runs it (patch output rows skipped by the deep sweep)
     bool band_prev_par = false;  // the last band cycle ran it (its deep sweep ended on ev_deep)
-    std::vector<iblb::SkipBox> band_skip;  // the plan's patch output regions (own columns, even rows)
     hipEvent_t ev_deep = nullptr;  // the last band cycle's deep sweep done (PAR cycles)
     int band_reserve = 0;        // CUs of the band chain's stream (0: one stream, in sequence; -2: unmasked)
     bool band_sticky = false;    // keep the streams while a schedule runs

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "iblb_device.h"
+#include "skip_box.h"
 
 namespace iblb {
 
@@ -87,13 +88,7 @@ struct FusedArgs {
 };
 
 // Two iterations per launch (lbm_sweep.hip): g^t -> g^{t+2}, no IB force owed in between.
-// IB band cycle with its last level beside the deep sweep (and a group slab's boundary sweeps): a patch output region the
-// last level stores and the deep sweep must not: local columns [x0, x1] (inclusive) x rows [y0, y1)
-// (even bounds, so that a lane's two cells are both in or both out)
-struct SkipBox {
-    int x0, x1, y0, y1;
-};
-constexpr int MAX_SKIP = 96;
+// (SkipBox, MAX_SKIP: skip_box.h)
 
 // The deep sweep's build features (lbm_sweep_impl.h:launch_sweepk_vs picks the kernel build from them;
 // one that does not apply to a (type, cells per lane, layout) combination is ignored)
