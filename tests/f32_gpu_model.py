@@ -14,6 +14,8 @@ equilibrium part from the momentum rho u = m + F/2 itself and the rho-scaled con
 c + (rho - 1) c, so the float32-rounded rho = 1 + (rho - 1) enters only through 1/rho; "r03" the
 round-3 order (rho * constant, rho * (c.u)), which this emulation reproduces at the GPU's measured
 round-3 errors (K1 128^2, 1000 iterations: rho - 1 1.8e-4, u_x 1.2e-6, u_y 8.9e-5).
+`dtype=np.float64` runs the same operation order in double (what the order itself costs, without
+float32); `mutate` seeds one named error into the collide (MUTATIONS), for the regime tests' power check.
 """
 from __future__ import annotations
 
@@ -27,18 +29,36 @@ WD = np.array([4 / 9] + [1 / 9] * 4 + [1 / 36] * 4)
 PA, PB = (1, 2, 5, 6), (3, 4, 7, 8)  # pairs (iblb_device.h pair_a / pair_b)
 
 
+# Seeded errors (`mutate`) of the nonlinear and forcing terms, for the power check of the regime tests
+# (tests/test_regimes.py::test_regimes_discriminate): what a kernel subtly wrong in that term computes.
+MUTATIONS = {
+    "M1": "the quadratic term (c.u)^2 / (2 cs^4) without rho (Qa = oqa)",
+    "M2": "the -u^2 / (2 cs^2) term dropped (base = 0)",
+    "M3": "the forcing's u.F part dropped",
+    "M4": "the forcing's (c.u)(c.F) part dropped (hE = 0)",
+    "M5": "kguo = 1 - 1/(2 tau2) instead of 1 - 1/(2 tau)",
+    "M6": "c.u from the momentum m without F/2",
+}
+
+
 def fma(a, b, c):
-    return (np.asarray(a, f64) * np.asarray(b, f64) + np.asarray(c, f64)).astype(f32)
+    """Float32 operands: the fused result (see the module docstring).  Float64 operands (dtype=float64:
+    the same operation order in double): product and sum rounded separately, 1e-16 away from fused."""
+    t = np.result_type(a, b, c)
+    return (np.asarray(a, f64) * np.asarray(b, f64) + np.asarray(c, f64)).astype(t)
 
 
-def kconst(tau, tau2, gx, gy):
-    """make_kbase<float> / make_kforce<float> (iblb_device.h:167-210), contraction off."""
-    op, om = f32(1.0 / tau), f32(1.0 / tau2)
-    kk = f32(1.0 - 1.0 / (2.0 * tau))
-    ics2, ics4 = f32(1.0 / (C_S * C_S)), f32(1.0 / (C_S * C_S * C_S * C_S))
-    a2 = f32(1.0 / (2.0 * C_S * C_S * C_S * C_S))
-    k = {"omp": f32(1) - op, "opwr": op * f32(4.0 / 9), "a1": f32(1.0 / (2.0 * C_S * C_S))}
-    for cl, w in ((0, f32(1.0 / 9)), (1, f32(1.0 / 36))):
+def kconst(tau, tau2, gx, gy, dtype=np.float32, mutate=None):
+    """make_kbase<float> / make_kforce<float> (iblb_device.h:167-210), contraction off; dtype=float64:
+    make_kbase<double>."""
+    assert mutate is None or mutate in MUTATIONS, mutate
+    R = dtype  # the compute type: every constant below is folded in it
+    op, om = R(1.0 / tau), R(1.0 / tau2)
+    kk = R(1.0 - 1.0 / (2.0 * (tau2 if mutate == "M5" else tau)))
+    ics2, ics4 = R(1.0 / (C_S * C_S)), R(1.0 / (C_S * C_S * C_S * C_S))
+    a2 = R(1.0 / (2.0 * C_S * C_S * C_S * C_S))
+    k = {"omp": R(1) - op, "opwr": op * R(4.0 / 9), "a1": R(1.0 / (2.0 * C_S * C_S))}
+    for cl, w in ((0, R(1.0 / 9)), (1, R(1.0 / 36))):
         k[f"opw{cl}"] = op * w
         k[f"oqa{cl}"] = k[f"opw{cl}"] * a2
         k[f"omwi2{cl}"] = om * w * ics2
@@ -46,46 +66,55 @@ def kconst(tau, tau2, gx, gy):
         k[f"kwi4{cl}"] = kw * ics4
         k[f"kwi2{cl}"] = kw * ics2
         k[f"nck{cl}"] = -(ics2 * kw)
-    k["hs"] = f32(0.5) * k["omp"]
-    k["hd"] = f32(0.5) * (f32(1) - om)
-    Fx, Fy = f32(gx), f32(gy)
-    k["Fx"], k["Fy"], k["hFx"], k["hFy"] = Fx, Fy, f32(0.5) * Fx, f32(0.5) * Fy
+    k["hs"] = R(0.5) * k["omp"]
+    k["hd"] = R(0.5) * (R(1) - om)
+    Fx, Fy = R(gx), R(gy)
+    k["Fx"], k["Fy"], k["hFx"], k["hFy"] = Fx, Fy, R(0.5) * Fx, R(0.5) * Fy
     cF = (Fx, Fy, Fx + Fy, Fy - Fx)
     for p in range(4):
         cl = 0 if p < 2 else 1
-        k[f"hE{p}"] = cF[p] * k[f"kwi4{cl}"]
+        k[f"hE{p}"] = cF[p] * k[f"kwi4{cl}"] if mutate != "M4" else R(0)
         k[f"gO{p}"] = cF[p] * k[f"kwi2{cl}"]
     return k
 
 
-def relax(h, k, variant="gpu"):
-    """relax_cell<float, true> on arrays h[9, ...] of pulled deviations; returns h1."""
+def relax(h, k, variant="gpu", mutate=None):
+    """relax_cell<float, true> on arrays h[9, ...] of pulled deviations; returns h1.  The compute type is
+    h's (float32, or float64 for the same order in double)."""
+    R = h.dtype.type  # the compute type
     s = [h[PA[p]] + h[PB[p]] for p in range(4)]
     d = [h[PA[p]] - h[PB[p]] for p in range(4)]
     sm = h[0] + ((s[0] + s[1]) + (s[2] + s[3]))
     mx = d[0] + (d[2] - d[3])
     my = d[1] + (d[2] + d[3])
-    rho = f32(1) + sm
-    inv = (f64(1) / rho.astype(f64)).astype(f32)  # v_rcp_f32 + one Newton step
+    rho = R(1) + sm
+    inv = (f64(1) / rho.astype(f64)).astype(R)  # v_rcp_f32 + one Newton step
     jx, jy = mx + k["hFx"], my + k["hFy"]
     ux, uy = jx * inv, jy * inv
     usq = fma(uy, uy, ux * ux)
     uF = fma(uy, k["Fy"], ux * k["Fx"])
     base = (-usq) * k["a1"]
+    if mutate == "M2":
+        base = base * R(0)
+    if mutate == "M3":
+        uF = uF * R(0)
+    cux, cuy = (mx * inv, my * inv) if mutate == "M6" else (ux, uy)
     rb = fma(rho, base, sm)
     out = np.empty_like(h)
     out[0] = fma(k["omp"], h[0], rb * k["opwr"])
     P, Qa, Rm = [], [], []
     for cl in (0, 1):
         P.append(fma(rb, k[f"opw{cl}"], uF * k[f"nck{cl}"]))
-        if variant == "gpu":
+        if mutate == "M1":
+            Qa.append(k[f"oqa{cl}"] + R(0) * sm)
+        elif variant == "gpu":
             Qa.append(fma(sm, k[f"oqa{cl}"], k[f"oqa{cl}"]))
         else:
             Qa.append(rho * k[f"oqa{cl}"])
             Rm.append(rho * k[f"omwi2{cl}"])
     for p in range(4):
         cl = 0 if p < 2 else 1
-        cu = (ux, uy, ux + uy, uy - ux)[p]
+        cu = (cux, cuy, cux + cuy, cuy - cux)[p]
         E = fma(cu, fma(Qa[cl], cu, k[f"hE{p}"]), P[cl])
         if variant == "gpu":  # rho (c.u) = c.(m + F/2): no rho, no 1/rho in the odd part
             cj = (jx, jy, jx + jy, jy - jx)[p]
@@ -122,9 +151,9 @@ class F32GpuChannel:
     """No-IB channel from rho, u (reference layout); the boot iteration in float64 (the GPU boots
     from the given double fields), then float32 iterations in the kernels' order."""
 
-    def __init__(self, nx, ny, tau, tau2, rho, u, body_force, variant="gpu"):
-        self.nx, self.ny, self.variant = nx, ny, variant
-        self.k = kconst(tau, tau2, *body_force)
+    def __init__(self, nx, ny, tau, tau2, rho, u, body_force, variant="gpu", dtype=np.float32, mutate=None):
+        self.nx, self.ny, self.variant, self.mutate = nx, ny, variant, mutate
+        self.k = kconst(tau, tau2, *body_force, dtype=dtype, mutate=mutate)
         rho = np.asarray(rho, f64).reshape(ny, nx)
         u = np.asarray(u, f64)
         ux, uy = u[:nx * ny].reshape(ny, nx), u[nx * ny:].reshape(ny, nx)
@@ -146,7 +175,7 @@ class F32GpuChannel:
         for a, b in zip(PA, PB):
             g[a] = feq[a] + Fi[a]
             g[b] = feq[b] + Fi[b]
-        self.g = (g - WD[:, None, None]).astype(f32)
+        self.g = (g - WD[:, None, None]).astype(dtype)
         self.booted = False  # the boot collide above is the first iteration
 
     def step(self, n=1):
@@ -154,7 +183,7 @@ class F32GpuChannel:
             if not self.booted:
                 self.booted = True
                 continue
-            self.g = relax(pull(self.g), self.k, self.variant)
+            self.g = relax(pull(self.g), self.k, self.variant, self.mutate)
 
     def macro(self):
         """rho (= 1 + the deviation sum), u = (m + F/2)/rho, in float64 from the stored f32 state."""
