@@ -77,6 +77,14 @@ class Cilia(C.Structure):
     _fields_ = [("c_num", C.c_int), ("c_space", C.c_double), ("T", C.c_int), ("p_step", C.c_int)]
 
 
+class Window(C.Structure):
+    """struct iblb_window (include/iblb.h): the global cells (x0 + i*sx, y0 + j*sy), i < nx, j < ny."""
+    _fields_ = [("x0", C.c_int), ("y0", C.c_int), ("nx", C.c_int), ("ny", C.c_int), ("sx", C.c_int), ("sy", C.c_int)]
+
+
+# IBLB_FIELD_* bits of iblb_get_fields, in ascending bit order (the order of the output planes)
+FIELDS = {"rho": 1, "ux": 2, "uy": 4, "vort": 8, "sxx": 16, "sxy": 32, "syy": 64}
+
 _vp = C.c_void_p
 _SIGS = {
     # (1) reference-shaped kernels: device pointers + stream
@@ -112,6 +120,8 @@ _SIGS = {
     "iblb_get_flux": ([_vp, C.POINTER(C.c_double)], C.c_int),
     "iblb_get_step": ([_vp, C.POINTER(C.c_longlong)], C.c_int),
     "iblb_count_nonfinite": ([_vp, C.POINTER(C.c_longlong)], C.c_int),
+    "iblb_window_local": ([_vp, C.POINTER(Window), C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
+    "iblb_get_fields": ([_vp, C.POINTER(Window), C.c_uint, _vp], C.c_int),
     "iblb_set_profiling": ([_vp, C.c_int], C.c_int),
     "iblb_get_timing": ([_vp, C.POINTER(Timing), C.c_int], C.c_int),
     "iblb_get_timing_ex": ([_vp, C.POINTER(Timing), C.c_ulong, C.c_int], C.c_int),

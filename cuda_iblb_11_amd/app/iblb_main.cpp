@@ -17,7 +17,9 @@
 //
 // Extensions (environment): IBLB_PRECISION=f32 stores populations in float; IBLB_CHECKPOINT=<prefix>
 // with IBLB_CHECKPOINT_EVERY=<iterations> writes <prefix>.rank<r> checkpoints; IBLB_RESTART=<prefix>
-// resumes from them (flux file appended, not truncated).
+// resumes from them (flux file appended, not truncated); IBLB_FIELDS_STRIDE=sx[,sy] (one GPU) also writes
+// <it>-fields.dat beside every <it>-fluid.dat: every sx-th column and sy-th row through iblb_get_fields,
+// x  y  u_x  u_y  vorticity (scaled like the fluid file), then the shear stress sxy in lattice units.
 #include <sys/stat.h>
 #include <sys/time.h>
 #include <unistd.h>
@@ -162,6 +164,21 @@ int main(int argc, char* argv[]) {
         return 1;
     }
 
+    // windowed field output (extension): stride of the samples, 0 = off
+    int fsx = 0, fsy = 0;
+    if (const char* fs = getenv("IBLB_FIELDS_STRIDE"); fs && *fs) {
+        const int n = sscanf(fs, "%d,%d", &fsx, &fsy);
+        if (n == 1) fsy = fsx;
+        if (n < 1 || fsx < 1 || fsy < 1) {
+            if (lead) cerr << "IBLB_FIELDS_STRIDE must be sx[,sy] with sx, sy >= 1, got " << fs << endl;
+            return 2;
+        }
+        if (world > 1) {  // vorticity needs the neighbour slabs' velocity: a lone slab only (include/iblb.h)
+            if (lead) cerr << "IBLB_FIELDS_STRIDE is not available under a launcher (WORLD_SIZE > 1): run on one GPU" << endl;
+            return 2;
+        }
+    }
+
     const double dx = 1. / LENGTH;
     const double dt = 1. / (T);
     const double SPEED = 0.8 * 1000 / T;
@@ -271,7 +288,15 @@ int main(int argc, char* argv[]) {
         cout << "Running Simulation...\n";
     }
 
-    std::vector<double> rho, u;
+    std::vector<double> rho, u, fld;
+    iblb_window fwin{0, 0, 1, 1, 1, 1};
+    if (fsx > 0) {
+        fwin.nx = ((int)XDIM - 1) / fsx + 1;
+        fwin.ny = ((int)YDIM - 1) / fsy + 1;
+        fwin.sx = fsx;
+        fwin.sy = fsy;
+        if (BigData) fld.resize(4 * (size_t)fwin.nx * fwin.ny);
+    }
     std::vector<float> s, u_s;
     std::vector<int> epsilon;
     if (lead && BigData) {
@@ -334,6 +359,24 @@ int main(int argc, char* argv[]) {
                         if (x == (int)XDIM - 1) fsA << endl;
                     }
                     fsA.close();
+                    if (fsx > 0) {
+                        if ((rc = iblb_get_fields(ctx, &fwin, IBLB_FIELD_UX | IBLB_FIELD_UY | IBLB_FIELD_VORT | IBLB_FIELD_SXY,
+                                                  fld.data())))
+                            return die(ctx, rc, "iblb_get_fields");
+                        const size_t np = (size_t)fwin.nx * fwin.ny;
+                        outfile = raw_data + to_string(it) + "-fields.dat";
+                        fsA.open(outfile.c_str());
+                        for (int j = 0; j < fwin.ny; j++) {
+                            for (int i = 0; i < fwin.nx; i++) {
+                                const size_t k = (size_t)j * fwin.nx + i;
+                                fsA << i * fsx * x_scale << "\t" << j * fsy * x_scale << "\t" << fld[k] * s_scale << "\t"
+                                    << fld[np + k] * s_scale << "\t" << fld[2 * np + k] * s_scale / x_scale << "\t"
+                                    << fld[3 * np + k] << "\n";
+                            }
+                            fsA << "\n";
+                        }
+                        fsA.close();
+                    }
                     if ((rc = iblb_get_lagrangian(ctx, s.data(), u_s.data(), epsilon.data())))
                         return die(ctx, rc, "iblb_get_lagrangian");
                     outfile = cilia_data + to_string(it) + "-cilia.dat";

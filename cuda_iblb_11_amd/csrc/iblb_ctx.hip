@@ -765,6 +765,87 @@ int iblb_count_nonfinite(iblb_ctx* c, long long* count) {
     return IBLB_OK;
 }
 
+// ---- windowed field readback ----------------------------------------------------------------------
+// The window (NULL: the whole lattice at stride 1) checked against the lattice, and the samples whose
+// column this slab owns: [*i_first, *i_first + *nxl) of the window's nx.
+static int window_part(iblb_ctx* c, const iblb_window* w, iblb_window* win, int* i_first, int* nxl) {
+    *win = w ? *w : iblb_window{0, 0, c->nx, c->ny, 1, 1};
+    if (win->sx < 1 || win->sy < 1 || win->nx < 1 || win->ny < 1 || win->x0 < 0 || win->y0 < 0 ||
+        (long long)win->x0 + (long long)(win->nx - 1) * win->sx >= c->nx ||
+        (long long)win->y0 + (long long)(win->ny - 1) * win->sy >= c->ny)
+        return fail(c, IBLB_ERR_ARG, "window: need sx, sy, nx, ny >= 1 and every sample inside the lattice (no wrap)");
+    // first sample at or right of x_begin, first sample at or right of the slab's end
+    auto first_at = [&](long long x) {
+        const long long i = x <= win->x0 ? 0 : (x - win->x0 + win->sx - 1) / win->sx;
+        return (int)std::min(i, (long long)win->nx);
+    };
+    const int lo = first_at(c->x_begin), hi = first_at((long long)c->x_begin + c->ncol);
+    *i_first = lo;
+    *nxl = hi - lo;
+    return IBLB_OK;
+}
+
+int iblb_window_local(iblb_ctx* c, const iblb_window* w, int* i_first, int* nx_local) {
+    if (!c) return IBLB_ERR_ARG;
+    iblb_window win;
+    int lo = 0, n = 0;
+    int rc = window_part(c, w, &win, &lo, &n);
+    if (rc) return rc;
+    if (i_first) *i_first = lo;
+    if (nx_local) *nx_local = n;
+    return IBLB_OK;
+}
+
+int iblb_get_fields(iblb_ctx* c, const iblb_window* w, unsigned fields, double* out) {
+    if (!c) return IBLB_ERR_ARG;
+    const unsigned known = IBLB_FIELD_RHO | IBLB_FIELD_UX | IBLB_FIELD_UY | IBLB_FIELD_VORT | IBLB_FIELD_SXX |
+                           IBLB_FIELD_SXY | IBLB_FIELD_SYY;
+    if (fields == 0 || (fields & ~known)) return fail(c, IBLB_ERR_ARG, "fields: no field or an unknown IBLB_FIELD_* bit");
+    iblb_window win;
+    int lo = 0, nxl = 0;
+    int rc = window_part(c, w, &win, &lo, &nxl);
+    if (rc) return rc;
+    if (nxl > 0 && !out) return fail(c, IBLB_ERR_ARG, "out is NULL");
+    if ((fields & IBLB_FIELD_VORT) && !single_slab(c))
+        return fail(c, IBLB_ERR_UNSUPPORTED,
+                    "vorticity needs the neighbour slabs' velocity and force: a lone slab only (compute it from "
+                    "the gathered u)");
+    if ((rc = prepare_read(c))) return rc;
+    if (nxl == 0) return IBLB_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int nf = __builtin_popcount(fields);
+    const size_t nb = (size_t)nf * win.ny * nxl * sizeof(double);
+    FieldsArgs a{};
+    a.xl0 = win.x0 + lo * win.sx - c->x_begin;
+    a.sx = win.sx;
+    a.nxl = nxl;
+    a.y0 = win.y0;
+    a.sy = win.sy;
+    a.nyw = win.ny;
+    a.fields = fields;
+    a.fplane = c->fplane;
+    a.gx = c->coef.gx;
+    a.gy = c->coef.gy;
+    a.kvisc = -c->coef.kguo;
+    if (c->phase == PH_BOOT) {
+        a.rho0 = c->rho0;
+        a.u0 = c->u0;
+    } else {
+        a.fdense = c->ib_state == IB_READY ? c->fdense : nullptr;
+    }
+    DevBuf d;
+    HIP_TRY(c, hipMalloc(&d.p, nb));
+    if (is_f64(c))
+        HIP_TRY(c, launch_fields_out<double>(gptr<double>(c, c->cur), c->L, halo_of<double>(c, c->cur), a, (double*)d.p,
+                                             c->stream));
+    else
+        HIP_TRY(c, launch_fields_out<float>(gptr<float>(c, c->cur), c->L, halo_of<float>(c, c->cur), a, (double*)d.p,
+                                            c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(out, d.p, nb, hipMemcpyDeviceToHost));
+    return IBLB_OK;
+}
+
 int iblb_get_step(iblb_ctx* c, long long* steps) {
     if (!c || !steps) return IBLB_ERR_ARG;
     *steps = c->t;

@@ -185,6 +185,24 @@ hipError_t launch_macro_out(const T* g, Layout L, Halo<T> H, const double* fdens
 template <typename T>
 hipError_t launch_pop_out(const T* g, Layout L, Halo<T> H, double* f, int raw, hipStream_t s);
 
+// Windowed field readback (field_kernels.hip; include/iblb.h iblb_get_fields).  Sample (il, j) is the
+// slab's cell (xl0 + il*sx, y0 + j*sy); plane k of out (the k-th set bit of `fields`) holds it at
+// [(k*nyw + j)*nxl + il].
+struct FieldsArgs {
+    int xl0, sx, nxl;         // first sampled local column, stride, samples along x
+    int y0, sy, nyw;          // first sampled row, stride, samples along y
+    unsigned fields;          // IBLB_FIELD_* bits
+    const double* fdense;     // dense IB force of the current state (nullptr: none)
+    long fplane;
+    double gx, gy;            // uniform body force
+    const double* rho0;       // boot phase: rho^0 / u^0 (slab layout, plane stride fplane) instead of the
+    const double* u0;         // moments, and the populations read in place (nullptr: run phase)
+    double kvisc;             // -(1 - 1/(2 TAU)): stress = kvisc * PiNeq
+};
+// Vorticity (IBLB_FIELD_VORT) wraps the neighbour columns modulo ncol: a lone slab only.
+template <typename T>
+hipError_t launch_fields_out(const T* g, Layout L, Halo<T> H, const FieldsArgs& a, double* out, hipStream_t s);
+
 // q(u^t) of the current state for the flux column (added to *out).
 template <typename T>
 hipError_t launch_flux(const T* g, Layout L, Halo<T> H, const double* fdense, long fplane,

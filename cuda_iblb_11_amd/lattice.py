@@ -22,6 +22,14 @@ def _ptr(a: np.ndarray | None):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _window(w):
+    """None, an L.Window or (x0, y0, nx, ny, sx, sy) as an L.Window (or None)."""
+    if w is None or isinstance(w, L.Window):
+        return w
+    x0, y0, nx, ny, sx, sy = (int(v) for v in w)
+    return L.Window(x0, y0, nx, ny, sx, sy)
+
+
 # ---- reference parameter derivation (main.cu:296-321) -------------------------------------
 
 C_S_DRIVER = 0.577  # main.cu:27 (the kernels use 0.57735, LatticeBoltzmann.cu:11)
@@ -240,6 +248,31 @@ class Lattice:
         self._check(self._lib.iblb_get_flux(self._h, C.byref(q)))
         return q.value
 
+    def window_local(self, window=None) -> tuple[int, int]:
+        """(i_first, nx_local): the samples of `window` whose column this slab owns
+        (iblb_window_local).  window: None (whole lattice), an L.Window or (x0, y0, nx, ny, sx, sy)."""
+        w = _window(window)
+        i0, n = C.c_int(0), C.c_int(0)
+        self._check(self._lib.iblb_window_local(self._h, None if w is None else C.byref(w), C.byref(i0), C.byref(n)))
+        return i0.value, n.value
+
+    def fields(self, names, window=None) -> dict:
+        """Fields on a strided window, computed on the device and copied out at the window's size
+        (iblb_get_fields).  names: any of "rho", "ux", "uy", "vort", "sxx", "sxy", "syy"; returns
+        {name: array (ny, nx_local)} of this slab's samples (collective in an RCCL group)."""
+        names = [names] if isinstance(names, str) else list(names)
+        unknown = [n for n in names if n not in L.FIELDS]
+        if unknown or not names:
+            raise ValueError(f"fields must be chosen from {sorted(L.FIELDS)}, got {names}")
+        w = _window(window)
+        _, nxl = self.window_local(w)
+        ny = self.ny if w is None else w.ny
+        order = sorted(set(names), key=L.FIELDS.get)
+        bits = sum(L.FIELDS[n] for n in order)
+        out = np.empty((len(order), ny, nxl))
+        self._check(self._lib.iblb_get_fields(self._h, None if w is None else C.byref(w), bits, _ptr(out)))
+        return {n: out[k] for k, n in enumerate(order)}
+
     @property
     def steps(self) -> int:
         n = C.c_longlong(0)
@@ -338,6 +371,12 @@ class LocalGroup:
             rho[:, s.x_begin:s.x_begin + s.x_count] = r.reshape(ny, s.x_count)
             u[:, :, s.x_begin:s.x_begin + s.x_count] = uu.reshape(2, ny, s.x_count)
         return rho.ravel(), u.reshape(2, -1).ravel()
+
+    def fields(self, names, window=None) -> dict:
+        """Lattice.fields of every slab, joined along x: {name: array (ny, nx)} of the window.
+        "vort" raises IBLB_ERR_UNSUPPORTED (a slab of a group does not compute it)."""
+        parts = [s.fields(names, window) for s in self.slabs]
+        return {n: np.concatenate([p[n] for p in parts], axis=1) for n in parts[0]}
 
     @property
     def flux(self) -> float:

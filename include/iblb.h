@@ -243,6 +243,37 @@ int iblb_get_step(iblb_ctx* ctx, long long* steps);
  * at every output iteration (the reference's penalty IB can diverge). */
 int iblb_count_nonfinite(iblb_ctx* ctx, long long* count);
 
+/* Windowed field readback: chosen fields on a strided window of the lattice, computed on the device
+ * and copied out at the window's size (not the lattice's).  The window samples the global cells
+ * (x0 + i*sx, y0 + j*sy), i < nx, j < ny: sx, sy >= 1, nx, ny >= 1, every sampled cell inside
+ * [0, XDIM) x [0, YDIM); the window never wraps.  NULL means the whole lattice at stride 1. */
+typedef struct iblb_window { int x0, y0, nx, ny, sx, sy; } iblb_window;   /* global cells x0+i*sx, y0+j*sy */
+#define IBLB_FIELD_RHO 1   /* as iblb_get_macro */
+#define IBLB_FIELD_UX  2
+#define IBLB_FIELD_UY  4
+#define IBLB_FIELD_VORT 8  /* d(uy)/dx - d(ux)/dy */
+#define IBLB_FIELD_SXX 16  /* viscous stress -(1 - 1/(2 TAU)) * PiNeq_ab */
+#define IBLB_FIELD_SXY 32
+#define IBLB_FIELD_SYY 64
+/* The samples of window w whose column this context owns: sample indices [*i_first, *i_first +
+ * *nx_local) of the window's nx (nx_local may be 0; either pointer may be NULL). */
+int iblb_window_local(iblb_ctx* ctx, const iblb_window* w, int* i_first, int* nx_local);
+/* For the k-th set bit of `fields` in ascending bit order, out[(k*ny + j)*nx_local + il] is that field
+ * at sample (i_first + il, j).  nx_local == 0: IBLB_OK, nothing written.  fields == 0, an unknown bit, a
+ * bad window, or out == NULL with nx_local > 0: IBLB_ERR_ARG (checked before anything collective).
+ * Valid in every phase, before the first step included.  Every field is a function of exactly what
+ * iblb_get_macro (rho, u with the force/2 correction) and iblb_get_populations (f) return at that moment:
+ *   PiNeq_ab = sum_i c_ia c_ib (f_i - feq_i(rho, u)), feq the reference equilibrium
+ *   (LatticeBoltzmann.cu:45-49, C_S = 0.57735) evaluated in double; the O(u F) term that Guo forcing
+ *   adds to the second moment is left out of the stress.
+ *   Vorticity: central differences of u at lattice spacing 1 whatever the stride, periodic in x; at
+ *   y = 0 and y = YDIM-1 the one-sided first difference.
+ * Vorticity needs the neighbour columns' u and force: a lone slab computes it; a slab of a local or
+ * RCCL group returns IBLB_ERR_UNSUPPORTED when IBLB_FIELD_VORT is set (every other field works).
+ * Goes through the same preparation as every reader: collective in an RCCL group, where each rank
+ * receives its own samples. */
+int iblb_get_fields(iblb_ctx* ctx, const iblb_window* w, unsigned fields, double* out);
+
 /* Timing: when enabled (1) every collide-stream launch is bracketed by HIP events on the
  * stream it runs on; iblb_get_timing() returns the sums (and resets them if reset).  enabled = 2:
  * only the deep (K-iteration) launches are timed, by their own dispatch / completion signals (no
