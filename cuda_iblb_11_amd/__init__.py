@@ -5,12 +5,12 @@ This package is the host-side mirror of that boundary: `Lattice` (fused context 
 `LocalGroup` / `Lattice.attach_rccl` (x-slab decomposition) and `kernels` (reference-named
 drop-in kernels on device tensors).  There is no CPU fallback.
 """
-from ._lib import (FIELDS, IBLB_ERR_ARG, IBLB_ERR_COMM, IBLB_ERR_STATE, IBLB_ERR_UNSUPPORTED, IblbError, Window,
+from ._lib import (FIELDS, QUANTITIES, IBLB_ERR_ARG, IBLB_ERR_COMM, IBLB_ERR_STATE, IBLB_ERR_UNSUPPORTED, IblbError, Window,
                    device_count, load)
-from .lattice import (Lattice, LocalGroup, RefParams, plan_slabs, rccl_unique_id, reference_taus,
+from .lattice import (Lattice, LocalGroup, RefParams, Stats, combine_stats, plan_slabs, rccl_unique_id, reference_taus,
                       split_populations, split_state)
 
 __all__ = [
-    "FIELDS", "IBLB_ERR_ARG", "IBLB_ERR_COMM", "IBLB_ERR_STATE", "IBLB_ERR_UNSUPPORTED", "IblbError", "Window", "device_count", "load", "Lattice", "LocalGroup", "RefParams", "plan_slabs",
-    "rccl_unique_id", "reference_taus", "split_populations", "split_state",
+    "FIELDS", "QUANTITIES", "IBLB_ERR_ARG", "IBLB_ERR_COMM", "IBLB_ERR_STATE", "IBLB_ERR_UNSUPPORTED", "IblbError", "Window", "device_count", "load", "Lattice", "LocalGroup", "RefParams", "plan_slabs",
+    "Stats", "combine_stats", "rccl_unique_id", "reference_taus", "split_populations", "split_state",
 ]

@@ -84,6 +84,19 @@ class Window(C.Structure):
 
 # IBLB_FIELD_* bits of iblb_get_fields, in ascending bit order (the order of the output planes)
 FIELDS = {"rho": 1, "ux": 2, "uy": 4, "vort": 8, "sxx": 16, "sxy": 32, "syy": 64}
+# what iblb_reduce_fields accepts: the fields and the reduce-only IBLB_QTY_* bits, in ascending bit order
+QUANTITIES = {**FIELDS, "momx": 128, "momy": 256, "ke": 512, "usq": 1024}
+
+
+class FieldStats(C.Structure):
+    """struct iblb_field_stats (include/iblb.h)."""
+    _fields_ = [
+        ("count", C.c_longlong), ("nonfinite", C.c_longlong),
+        ("sum", C.c_double), ("sum_sq", C.c_double),
+        ("min", C.c_double), ("max", C.c_double),
+        ("min_i", C.c_int), ("min_j", C.c_int), ("max_i", C.c_int), ("max_j", C.c_int),
+    ]
+
 
 _vp = C.c_void_p
 _SIGS = {
@@ -122,6 +135,7 @@ _SIGS = {
     "iblb_count_nonfinite": ([_vp, C.POINTER(C.c_longlong)], C.c_int),
     "iblb_window_local": ([_vp, C.POINTER(Window), C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
     "iblb_get_fields": ([_vp, C.POINTER(Window), C.c_uint, _vp], C.c_int),
+    "iblb_reduce_fields": ([_vp, C.POINTER(Window), C.c_uint, C.POINTER(FieldStats), _vp, _vp], C.c_int),
     "iblb_set_profiling": ([_vp, C.c_int], C.c_int),
     "iblb_get_timing": ([_vp, C.POINTER(Timing), C.c_int], C.c_int),
     "iblb_get_timing_ex": ([_vp, C.POINTER(Timing), C.c_ulong, C.c_int], C.c_int),

@@ -19,7 +19,10 @@
 // with IBLB_CHECKPOINT_EVERY=<iterations> writes <prefix>.rank<r> checkpoints; IBLB_RESTART=<prefix>
 // resumes from them (flux file appended, not truncated); IBLB_FIELDS_STRIDE=sx[,sy] (one GPU) also writes
 // <it>-fields.dat beside every <it>-fluid.dat: every sx-th column and sy-th row through iblb_get_fields,
-// x  y  u_x  u_y  vorticity (scaled like the fluid file), then the shear stress sxy in lattice units.
+// x  y  u_x  u_y  vorticity (scaled like the fluid file), then the shear stress sxy in lattice units;
+// IBLB_STATS=1 (one GPU) appends one line per output iteration to <..>-stats.dat beside the flux file, from one
+// iblb_reduce_fields call over the whole lattice (lattice units, %.17g; BigData or not):
+// it  sum(rho)  sum(rho u_x)  sum(rho u_y)  sum(KE)  max(u^2)  x  y  Ma = sqrt(max u^2)/0.57735  non-finite rho samples
 #include <sys/stat.h>
 #include <sys/time.h>
 #include <unistd.h>
@@ -179,6 +182,13 @@ int main(int argc, char* argv[]) {
         }
     }
 
+    // whole-lattice statistics at every output iteration (extension)
+    const bool stats_on = env_int("IBLB_STATS", 0) != 0;
+    if (stats_on && world > 1) {  // each rank would reduce its own slab only: combining them is not the driver's yet
+        if (lead) cerr << "IBLB_STATS is not available under a launcher (WORLD_SIZE > 1): run on one GPU" << endl;
+        return 2;
+    }
+
     const double dx = 1. / LENGTH;
     const double dt = 1. / (T);
     const double SPEED = 0.8 * 1000 / T;
@@ -257,6 +267,7 @@ int main(int argc, char* argv[]) {
     const std::string flux = output_data + "/Flux/" + to_string(c_fraction) + "_" + to_string(c_num) + "_" +
                              to_string(c_space) + "_" + to_string_3(Re) + "_" + to_string_3(T_num) + "x" +
                              to_string_3(T_pow) + "-flux.dat";
+    const std::string stats_path = flux.substr(0, flux.size() - strlen("-flux.dat")) + "-stats.dat";
     const std::string parameters = raw_data + "/SimLog.txt";
 
     ofstream fsA, fsB, fsC;
@@ -267,6 +278,10 @@ int main(int argc, char* argv[]) {
         if (restart.empty()) {
             fsB.open(flux.c_str(), ofstream::trunc);
             fsB.close();
+            if (stats_on) {
+                fsB.open(stats_path.c_str(), ofstream::trunc);
+                fsB.close();
+            }
         }
         //-----------------------------------OUTPUT PARAMETERS----------------------------- (main.cu:761-790)
         fsC.open(parameters.c_str(), ofstream::trunc);
@@ -388,6 +403,21 @@ int main(int argc, char* argv[]) {
                     }
                     fsA.close();
                 }
+            }
+            if (stats_on) {
+                iblb_field_stats st[5];  // ascending bit order: rho, momx, momy, ke, usq
+                if ((rc = iblb_reduce_fields(ctx, nullptr, IBLB_FIELD_RHO | IBLB_QTY_MOMX | IBLB_QTY_MOMY | IBLB_QTY_KE | IBLB_QTY_USQ,
+                                             st, nullptr, nullptr)))
+                    return die(ctx, rc, "iblb_reduce_fields");
+                FILE* fs = fopen(stats_path.c_str(), "a");
+                if (!fs) {
+                    fprintf(stderr, "cannot append to %s: %s\n", stats_path.c_str(), strerror(errno));
+                    return 1;
+                }
+                fprintf(fs, "%u\t%.17g\t%.17g\t%.17g\t%.17g\t%.17g\t%d\t%d\t%.17g\t%lld\n", it, st[0].sum, st[1].sum,
+                        st[2].sum, st[3].sum, st[4].max, st[4].max_i, st[4].max_j, sqrt(st[4].max) / 0.57735,
+                        st[0].nonfinite);
+                fclose(fs);
             }
             if ((rc = iblb_get_flux(ctx, &Q))) return die(ctx, rc, "iblb_get_flux");
             if (lead) {

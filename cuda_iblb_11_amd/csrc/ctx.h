@@ -157,6 +157,11 @@ struct iblb_ctx {
     hipEvent_t ev_b0 = nullptr, ev_bd = nullptr;
     // flux: d_Q[0] cumulative, d_Q[1] scratch
     double* d_Q = nullptr;
+    // iblb_reduce_fields: device scratch (partials and result, ReduceGeom) and the host copy of the result;
+    // both grow on demand and stay with the context
+    double* red_buf = nullptr;
+    size_t red_cap = 0;  // doubles allocated
+    std::vector<double> red_host;
     // state machine
     int phase = iblbh::PH_EMPTY;
     long long t = 0;

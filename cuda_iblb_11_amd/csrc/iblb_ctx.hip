@@ -461,7 +461,7 @@ void iblb_destroy(iblb_ctx* c) {
         if (e) (void)hipEventDestroy(e);
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     void* bufs[] = {c->g_alloc, c->cil_samples, c->cil_lasts, c->cil_bpoints, c->rho0, c->u0, c->force0, c->d_s,
-                    c->d_us, c->d_Fs, c->d_eps, c->d_Fs_sum, c->fd_alloc, c->fl_alloc, c->d_Q, c->d_sch_s,
+                    c->d_us, c->d_Fs, c->d_eps, c->d_Fs_sum, c->fd_alloc, c->fl_alloc, c->d_Q, c->red_buf, c->d_sch_s,
                     c->d_sch_us, c->d_sch_eps};
     for (void* p : bufs)
         if (p) (void)hipFree(p);
@@ -796,6 +796,29 @@ int iblb_window_local(iblb_ctx* c, const iblb_window* w, int* i_first, int* nx_l
     return IBLB_OK;
 }
 
+// The arguments of the windowed kernels for this slab's part of window win: samples [lo, lo + nxl)
+static FieldsArgs window_args(iblb_ctx* c, const iblb_window& win, int lo, int nxl, unsigned fields) {
+    FieldsArgs a{};
+    a.xl0 = win.x0 + lo * win.sx - c->x_begin;
+    a.sx = win.sx;
+    a.nxl = nxl;
+    a.y0 = win.y0;
+    a.sy = win.sy;
+    a.nyw = win.ny;
+    a.fields = fields;
+    a.fplane = c->fplane;
+    a.gx = c->coef.gx;
+    a.gy = c->coef.gy;
+    a.kvisc = -c->coef.kguo;
+    if (c->phase == PH_BOOT) {
+        a.rho0 = c->rho0;
+        a.u0 = c->u0;
+    } else {
+        a.fdense = c->ib_state == IB_READY ? c->fdense : nullptr;
+    }
+    return a;
+}
+
 int iblb_get_fields(iblb_ctx* c, const iblb_window* w, unsigned fields, double* out) {
     if (!c) return IBLB_ERR_ARG;
     const unsigned known = IBLB_FIELD_RHO | IBLB_FIELD_UX | IBLB_FIELD_UY | IBLB_FIELD_VORT | IBLB_FIELD_SXX |
@@ -815,24 +838,7 @@ int iblb_get_fields(iblb_ctx* c, const iblb_window* w, unsigned fields, double* 
     HIP_TRY(c, hipSetDevice(c->device));
     const int nf = __builtin_popcount(fields);
     const size_t nb = (size_t)nf * win.ny * nxl * sizeof(double);
-    FieldsArgs a{};
-    a.xl0 = win.x0 + lo * win.sx - c->x_begin;
-    a.sx = win.sx;
-    a.nxl = nxl;
-    a.y0 = win.y0;
-    a.sy = win.sy;
-    a.nyw = win.ny;
-    a.fields = fields;
-    a.fplane = c->fplane;
-    a.gx = c->coef.gx;
-    a.gy = c->coef.gy;
-    a.kvisc = -c->coef.kguo;
-    if (c->phase == PH_BOOT) {
-        a.rho0 = c->rho0;
-        a.u0 = c->u0;
-    } else {
-        a.fdense = c->ib_state == IB_READY ? c->fdense : nullptr;
-    }
+    const FieldsArgs a = window_args(c, win, lo, nxl, fields);
     DevBuf d;
     HIP_TRY(c, hipMalloc(&d.p, nb));
     if (is_f64(c))
@@ -843,6 +849,71 @@ int iblb_get_fields(iblb_ctx* c, const iblb_window* w, unsigned fields, double* 
                                             c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipMemcpy(out, d.p, nb, hipMemcpyDeviceToHost));
+    return IBLB_OK;
+}
+
+// ---- window reduction ---------------------------------------------------------------------------------
+int iblb_reduce_fields(iblb_ctx* c, const iblb_window* w, unsigned fields, iblb_field_stats* stats, double* row_sum,
+                       double* col_sum) {
+    if (!c) return IBLB_ERR_ARG;
+    const unsigned known = IBLB_FIELD_RHO | IBLB_FIELD_UX | IBLB_FIELD_UY | IBLB_FIELD_VORT | IBLB_FIELD_SXX |
+                           IBLB_FIELD_SXY | IBLB_FIELD_SYY | IBLB_QTY_MOMX | IBLB_QTY_MOMY | IBLB_QTY_KE | IBLB_QTY_USQ;
+    if (fields == 0 || (fields & ~known))
+        return fail(c, IBLB_ERR_ARG, "fields: no quantity or an unknown IBLB_FIELD_* / IBLB_QTY_* bit");
+    iblb_window win;
+    int lo = 0, nxl = 0;
+    int rc = window_part(c, w, &win, &lo, &nxl);
+    if (rc) return rc;
+    if (!stats) return fail(c, IBLB_ERR_ARG, "stats is NULL");
+    if ((fields & IBLB_FIELD_VORT) && !single_slab(c))
+        return fail(c, IBLB_ERR_UNSUPPORTED,
+                    "vorticity needs the neighbour slabs' velocity and force: a lone slab only (compute it from "
+                    "the gathered u)");
+    if ((rc = prepare_read(c))) return rc;
+    const int nf = __builtin_popcount(fields);
+    if (nxl == 0) {  // none of the window's columns is this slab's
+        for (int k = 0; k < nf; ++k)
+            stats[k] = iblb_field_stats{0, 0, 0., 0., HUGE_VAL, -HUGE_VAL, -1, -1, -1, -1};
+        if (row_sum) std::fill(row_sum, row_sum + (size_t)nf * win.ny, 0.);
+        return IBLB_OK;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    ReduceGeom q = reduce_geometry(nxl, win.ny, nf, row_sum != nullptr, col_sum != nullptr);
+    q.i_first = lo;
+    if ((size_t)q.n_scratch > c->red_cap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (c->red_buf) HIP_TRY(c, hipFree(c->red_buf));
+        c->red_buf = nullptr;
+        c->red_cap = 0;
+        if (hipMalloc((void**)&c->red_buf, (size_t)q.n_scratch * sizeof(double)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, IBLB_ERR_NOMEM, "iblb_reduce_fields: scratch allocation failed");
+        }
+        c->red_cap = (size_t)q.n_scratch;
+    }
+    const FieldsArgs a = window_args(c, win, lo, nxl, fields);
+    if (is_f64(c))
+        HIP_TRY(c, launch_reduce_fields<double>(gptr<double>(c, c->cur), c->L, halo_of<double>(c, c->cur), a, q,
+                                                c->red_buf, c->stream));
+    else
+        HIP_TRY(c, launch_reduce_fields<float>(gptr<float>(c, c->cur), c->L, halo_of<float>(c, c->cur), a, q,
+                                               c->red_buf, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->red_host.resize((size_t)q.n_out);
+    HIP_TRY(c, hipMemcpy(c->red_host.data(), c->red_buf + q.o_out, (size_t)q.n_out * sizeof(double),
+                         hipMemcpyDeviceToHost));
+    const double* h = c->red_host.data();
+    for (int k = 0; k < nf; ++k) {
+        const double* r = h + (size_t)k * REDUCE_RS;
+        stats[k] = iblb_field_stats{(long long)r[0], (long long)r[1], r[2], r[3], r[4], r[5],
+                                    (int)r[6], (int)r[7], (int)r[8], (int)r[9]};
+    }
+    h += (size_t)nf * REDUCE_RS;
+    if (row_sum) {
+        std::copy(h, h + (size_t)nf * win.ny, row_sum);
+        h += (size_t)nf * win.ny;
+    }
+    if (col_sum) std::copy(h, h + (size_t)nf * nxl, col_sum);
     return IBLB_OK;
 }
 

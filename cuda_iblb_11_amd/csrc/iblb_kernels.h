@@ -203,6 +203,36 @@ struct FieldsArgs {
 template <typename T>
 hipError_t launch_fields_out(const T* g, Layout L, Halo<T> H, const FieldsArgs& a, double* out, hipStream_t s);
 
+// Window reduction (reduce_kernels.hip; include/iblb.h iblb_reduce_fields): statistics, row sums and
+// column sums of the quantities in a.fields (the IBLB_FIELD_* and IBLB_QTY_* bits) over the samples of
+// FieldsArgs, each evaluated once by the device functions of field_eval.h.
+constexpr int REDUCE_NQ = 11;      // quantities: bit k of `fields`, k < 11
+constexpr int REDUCE_RS = 10;      // doubles of one statistics record: count, nonfinite, sum, sum_sq, min, max,
+                                   // min_i, min_j, max_i, max_j (integers below 2^53: exact)
+constexpr int REDUCE_ROWS = 256;   // window rows of one workgroup (one per lane, four waves)
+// Pass 1 runs rb x cb workgroups: workgroup (r, c) takes window rows [256 r, 256 r + 256) and the slab's
+// samples [cc c, cc c + cc) along x.  It leaves, each at its own fixed place in the scratch (doubles),
+//   at 0      one statistics record per (workgroup, quantity)         [c * rb + r][nf][REDUCE_RS]
+//   at o_row  one partial row sum per (column chunk, quantity, row)   [c][nf][nyw]        (rows)
+//   at o_col  one partial column sum per (wave of rows, quantity, x)  [4 r + wave][nf][nxl] (cols)
+// and pass 2, a launch of its own, adds them in ascending index order into the result at o_out:
+// [nf][REDUCE_RS] records, then [nf][nyw] row sums (rows), then [nf][nxl] column sums (cols).
+struct ReduceGeom {
+    int cc, cb, rb;
+    int nf;                    // quantities requested (set bits of a.fields)
+    int i_first;               // window index i of the slab's first sample (min_i / max_i are window indices)
+    int rows, cols;            // row sums / column sums wanted
+    long o_row, o_col, o_out;  // offsets in the scratch
+    long n_scratch, n_out;     // doubles of the whole scratch and of the result at its end
+};
+// The geometry for nxl x nyw samples (nxl, nyw >= 1): a function of the sizes and the request only.
+ReduceGeom reduce_geometry(int nxl, int nyw, int nf, bool rows, bool cols);
+// Both passes on stream s; the result is at scratch + q.o_out when they are done.  Vorticity as
+// launch_fields_out: a lone slab only.
+template <typename T>
+hipError_t launch_reduce_fields(const T* g, Layout L, Halo<T> H, const FieldsArgs& a, const ReduceGeom& q,
+                                double* scratch, hipStream_t s);
+
 // q(u^t) of the current state for the flux column (added to *out).
 template <typename T>
 hipError_t launch_flux(const T* g, Layout L, Halo<T> H, const double* fdense, long fplane,

@@ -30,6 +30,53 @@ def _window(w):
     return L.Window(x0, y0, nx, ny, sx, sy)
 
 
+@dataclass
+class Stats:
+    """One quantity's iblb_field_stats, plus its row sums [window ny] and column sums [nx_local]
+    (None where not asked for).  Indices are window sample indices; count == 0: min / max = +inf /
+    -inf and the indices -1."""
+    count: int = 0
+    nonfinite: int = 0
+    sum: float = 0.0
+    sum_sq: float = 0.0
+    min: float = math.inf
+    max: float = -math.inf
+    min_i: int = -1
+    min_j: int = -1
+    max_i: int = -1
+    max_j: int = -1
+    row_sum: np.ndarray | None = None
+    col_sum: np.ndarray | None = None
+
+
+def combine_stats(parts):
+    """Merge per-slab results of Lattice.reduce, given in slab order (left to right): a list of
+    {name: Stats} gives {name: Stats}, a list of Stats one Stats.  Counts and sums add; min / max
+    keep the lower / higher value and, among equal values, the sample with the lowest j, then the
+    lowest i (iblb_reduce_fields' tie rule); row sums add; column sums concatenate."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("combine_stats needs at least one part")
+    if isinstance(parts[0], dict):
+        return {n: combine_stats([p[n] for p in parts]) for n in parts[0]}
+    out = Stats()
+    for p in parts:
+        out.count += p.count
+        out.nonfinite += p.nonfinite
+        out.sum += p.sum
+        out.sum_sq += p.sum_sq
+        if p.count > 0:
+            if p.min < out.min or (p.min == out.min and (p.min_j, p.min_i) < (out.min_j, out.min_i)):
+                out.min, out.min_i, out.min_j = p.min, p.min_i, p.min_j
+            if p.max > out.max or (p.max == out.max and (p.max_j, p.max_i) < (out.max_j, out.max_i)):
+                out.max, out.max_i, out.max_j = p.max, p.max_i, p.max_j
+    if all(p.row_sum is not None for p in parts):
+        out.row_sum = np.sum([p.row_sum for p in parts], axis=0)
+    if all(p.col_sum is not None for p in parts):
+        out.col_sum = np.concatenate([p.col_sum for p in parts])
+    return out
+
+
 # ---- reference parameter derivation (main.cu:296-321) -------------------------------------
 
 C_S_DRIVER = 0.577  # main.cu:27 (the kernels use 0.57735, LatticeBoltzmann.cu:11)
@@ -273,6 +320,30 @@ class Lattice:
         self._check(self._lib.iblb_get_fields(self._h, None if w is None else C.byref(w), bits, _ptr(out)))
         return {n: out[k] for k, n in enumerate(order)}
 
+    def reduce(self, names, window=None, rows=False, cols=False) -> dict:
+        """Statistics of quantities over a strided window, reduced on the device (iblb_reduce_fields):
+        nothing of the window's size is copied.  names: any of L.QUANTITIES (the fields of `fields`
+        plus "momx", "momy", "ke", "usq"); returns {name: Stats} in ascending bit order, for this
+        slab's samples (collective in an RCCL group).  rows / cols: also the sums over this slab's i
+        of every window row (Stats.row_sum) / over j of every sample column (Stats.col_sum)."""
+        names = [names] if isinstance(names, str) else list(names)
+        unknown = [n for n in names if n not in L.QUANTITIES]
+        if unknown or not names:
+            raise ValueError(f"quantities must be chosen from {sorted(L.QUANTITIES)}, got {names}")
+        w = _window(window)
+        _, nxl = self.window_local(w)
+        ny = self.ny if w is None else w.ny
+        order = sorted(set(names), key=L.QUANTITIES.get)
+        bits = sum(L.QUANTITIES[n] for n in order)
+        st = (L.FieldStats * len(order))()
+        rs = np.zeros((len(order), ny)) if rows else None
+        cs = np.zeros((len(order), nxl)) if cols else None
+        self._check(self._lib.iblb_reduce_fields(self._h, None if w is None else C.byref(w), bits, st, _ptr(rs),
+                                                 _ptr(cs)))
+        return {n: Stats(*(getattr(st[k], f) for f, _ in L.FieldStats._fields_),
+                         row_sum=rs[k] if rows else None, col_sum=cs[k] if cols else None)
+                for k, n in enumerate(order)}
+
     @property
     def steps(self) -> int:
         n = C.c_longlong(0)
@@ -377,6 +448,11 @@ class LocalGroup:
         "vort" raises IBLB_ERR_UNSUPPORTED (a slab of a group does not compute it)."""
         parts = [s.fields(names, window) for s in self.slabs]
         return {n: np.concatenate([p[n] for p in parts], axis=1) for n in parts[0]}
+
+    def reduce(self, names, window=None, rows=False, cols=False) -> dict:
+        """Lattice.reduce of every slab merged by combine_stats: {name: Stats} of the whole window.
+        "vort" raises IBLB_ERR_UNSUPPORTED (a slab of a group does not compute it)."""
+        return combine_stats([s.reduce(names, window, rows, cols) for s in self.slabs])
 
     @property
     def flux(self) -> float:

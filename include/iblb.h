@@ -274,6 +274,40 @@ int iblb_window_local(iblb_ctx* ctx, const iblb_window* w, int* i_first, int* nx
  * receives its own samples. */
 int iblb_get_fields(iblb_ctx* ctx, const iblb_window* w, unsigned fields, double* out);
 
+/* Window reduction: statistics, row sums and column sums of chosen quantities over a window, computed on
+ * the device; what crosses to the host is O(nx + ny) values, not the window.  `w`, the seven IBLB_FIELD_*
+ * bits and the value of every sample are exactly those of iblb_get_fields (every phase, the boot phase
+ * included); four more quantities are accepted here only (iblb_get_fields refuses them), each the stated
+ * expression of that sample's rho, ux, uy with one rounding per operation: */
+#define IBLB_QTY_MOMX 128    /* rho*ux */
+#define IBLB_QTY_MOMY 256    /* rho*uy */
+#define IBLB_QTY_KE   512    /* 0.5*(rho*(ux*ux + uy*uy)), evaluated in exactly this order */
+#define IBLB_QTY_USQ  1024   /* ux*ux + uy*uy  (Ma^2 = max / C_S^2; no sqrt on the device) */
+typedef struct iblb_field_stats {
+    long long count;       /* finite samples reduced */
+    long long nonfinite;   /* NaN / Inf samples: counted here and left out of everything else */
+    double sum, sum_sq;
+    double min, max;       /* count == 0: +inf / -inf */
+    int min_i, min_j, max_i, max_j;  /* window sample indices (i of the window's nx, not slab-local); count == 0: -1 */
+} iblb_field_stats;
+/* stats[k] (and row k of row_sum, col_sum) belongs to the k-th set bit of `fields` in ascending bit order.
+ * This context reduces the samples whose column it owns (iblb_window_local): row_sum[k*w.ny + j] is the
+ * sum over its i of row j, col_sum[k*nx_local + il] the sum over j of its sample column il; either may be
+ * NULL (not computed).  min / max compare with < / >; among equal values the sample with the lowest j,
+ * then the lowest i, is reported (the first in row-major order).  A non-finite sample of a quantity is
+ * counted in `nonfinite` and is absent from that quantity's count, sums, extrema, row and column sums.
+ * nx_local == 0: IBLB_OK, empty statistics (count 0, +inf / -inf, -1), row_sum zeros, col_sum untouched.
+ * The result is a function of the state and the window alone (no floating-point atomics; fixed summation
+ * order): repeated calls return the same bits.  sum and sum_sq are within n * 2^-53 * sum |x| (sum x^2) of
+ * the exact sum of the n samples.
+ * fields == 0, an unknown bit, a bad window or stats == NULL: IBLB_ERR_ARG, checked before anything
+ * collective, no output touched.  IBLB_FIELD_VORT on a slab of a local or RCCL group: IBLB_ERR_UNSUPPORTED
+ * (as iblb_get_fields).  Collective in an RCCL group like every reader; each rank receives its own part
+ * (combining the parts is the caller's: counts and sums add, extrema follow the tie rule, row sums add,
+ * column sums concatenate in slab order). */
+int iblb_reduce_fields(iblb_ctx* ctx, const iblb_window* w, unsigned fields, iblb_field_stats* stats,
+                       double* row_sum, double* col_sum);
+
 /* Timing: when enabled (1) every collide-stream launch is bracketed by HIP events on the
  * stream it runs on; iblb_get_timing() returns the sums (and resets them if reset).  enabled = 2:
  * only the deep (K-iteration) launches are timed, by their own dispatch / completion signals (no
