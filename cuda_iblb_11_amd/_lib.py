@@ -136,6 +136,10 @@ _SIGS = {
     "iblb_window_local": ([_vp, C.POINTER(Window), C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
     "iblb_get_fields": ([_vp, C.POINTER(Window), C.c_uint, _vp], C.c_int),
     "iblb_reduce_fields": ([_vp, C.POINTER(Window), C.c_uint, C.POINTER(FieldStats), _vp, _vp], C.c_int),
+    "iblb_sample_points": ([_vp, C.c_int, _vp, _vp, C.c_uint, _vp], C.c_int),
+    "iblb_set_tracers": ([_vp, C.c_longlong, _vp, _vp, C.c_int], C.c_int),
+    "iblb_get_tracers": ([_vp, _vp, _vp, _vp], C.c_int),
+    "iblb_tracer_count": ([_vp, C.POINTER(C.c_longlong), C.POINTER(C.c_int), C.POINTER(C.c_longlong)], C.c_int),
     "iblb_set_profiling": ([_vp, C.c_int], C.c_int),
     "iblb_get_timing": ([_vp, C.POINTER(Timing), C.c_int], C.c_int),
     "iblb_get_timing_ex": ([_vp, C.POINTER(Timing), C.c_ulong, C.c_int], C.c_int),

@@ -23,6 +23,10 @@
 // IBLB_STATS=1 (one GPU) appends one line per output iteration to <..>-stats.dat beside the flux file, from one
 // iblb_reduce_fields call over the whole lattice (lattice units, %.17g; BigData or not):
 // it  sum(rho)  sum(rho u_x)  sum(rho u_y)  sum(KE)  max(u^2)  x  y  Ma = sqrt(max u^2)/0.57735  non-finite rho samples
+// IBLB_TRACERS=nx_t,ny_t[,stride] (one GPU) seeds passive tracers (iblb_set_tracers) on a regular nx_t x ny_t grid,
+// x = (i + 0.5) XDIM / nx_t, y = (j + 0.5) (YDIM - 1) / ny_t, tracer i * ny_t + j, updated every `stride` (default 1)
+// iterations, and writes <it>-tracers.dat beside the fluid files at every output iteration (BigData or not): one line
+// x  y  laps per tracer, lattice units, %.17g.  Checkpoints hold no tracers: a restarted run seeds the grid again.
 #include <sys/stat.h>
 #include <sys/time.h>
 #include <unistd.h>
@@ -189,6 +193,25 @@ int main(int argc, char* argv[]) {
         return 2;
     }
 
+    // passive tracers (extension): a regular grid of nx_t x ny_t, 0 = off
+    int tr_nx = 0, tr_ny = 0, tr_stride = 1;
+    if (const char* ts = getenv("IBLB_TRACERS"); ts && *ts) {
+        char tail = 0;
+        bool ok = sscanf(ts, "%d,%d,%d%c", &tr_nx, &tr_ny, &tr_stride, &tail) == 3;  // (a trailing character: 4)
+        if (!ok) {
+            tr_stride = 1;
+            ok = sscanf(ts, "%d,%d%c", &tr_nx, &tr_ny, &tail) == 2;
+        }
+        if (!ok || tr_nx < 1 || tr_ny < 1 || tr_stride < 1 || (long long)tr_nx * tr_ny > 100000000LL) {
+            if (lead) cerr << "IBLB_TRACERS must be nx_t,ny_t[,stride] with nx_t, ny_t, stride >= 1 and at most 1e8 tracers, got " << ts << endl;
+            return 2;
+        }
+        if (world > 1) {  // a tracer's four cells may straddle slabs: a lone slab only (include/iblb.h)
+            if (lead) cerr << "IBLB_TRACERS is not available under a launcher (WORLD_SIZE > 1): run on one GPU" << endl;
+            return 2;
+        }
+    }
+
     const double dx = 1. / LENGTH;
     const double dt = 1. / (T);
     const double SPEED = 0.8 * 1000 / T;
@@ -256,6 +279,20 @@ int main(int argc, char* argv[]) {
         long long t = 0;
         iblb_get_step(ctx, &t);
         it0 = (unsigned int)t;
+    }
+    // the tracer grid, seeded at the run's first iteration (a restarted run's too: checkpoints hold no tracers)
+    const size_t tr_n = (size_t)tr_nx * tr_ny;
+    std::vector<double> tr_x(tr_n), tr_y(tr_n);
+    std::vector<int> tr_laps(tr_n);
+    if (tr_n > 0) {
+        // y fastest, like the populations: neighbouring lanes of the update kernel read neighbouring rows
+        for (int i = 0; i < tr_nx; i++)
+            for (int j = 0; j < tr_ny; j++) {
+                tr_x[(size_t)i * tr_ny + j] = (i + 0.5) * XDIM / tr_nx;
+                tr_y[(size_t)i * tr_ny + j] = (j + 0.5) * (YDIM - 1) / tr_ny;
+            }
+        if ((rc = iblb_set_tracers(ctx, (long long)tr_n, tr_x.data(), tr_y.data(), tr_stride)))
+            return die(ctx, rc, "iblb_set_tracers");
     }
 
     //----------------------------------------DEFINE DIRECTORIES---------------------------------- (main.cu:589-631)
@@ -418,6 +455,18 @@ int main(int argc, char* argv[]) {
                         st[2].sum, st[3].sum, st[4].max, st[4].max_i, st[4].max_j, sqrt(st[4].max) / 0.57735,
                         st[0].nonfinite);
                 fclose(fs);
+            }
+            if (tr_n > 0) {
+                if ((rc = iblb_get_tracers(ctx, tr_x.data(), tr_y.data(), tr_laps.data())))
+                    return die(ctx, rc, "iblb_get_tracers");
+                outfile = raw_data + to_string(it) + "-tracers.dat";
+                FILE* ft = fopen(outfile.c_str(), "w");
+                if (!ft) {
+                    fprintf(stderr, "cannot write %s: %s\n", outfile.c_str(), strerror(errno));
+                    return 1;
+                }
+                for (size_t k = 0; k < tr_n; k++) fprintf(ft, "%.17g\t%.17g\t%d\n", tr_x[k], tr_y[k], tr_laps[k]);
+                fclose(ft);
             }
             if ((rc = iblb_get_flux(ctx, &Q))) return die(ctx, rc, "iblb_get_flux");
             if (lead) {

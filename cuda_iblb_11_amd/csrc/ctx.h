@@ -1,6 +1,6 @@
 // ctx.h — the context of the fused C ABI (include/iblb.h part 2) and the host helpers shared by
 // its translation units:
-//   iblb_ctx.hip   lifecycle, state, Lagrangian points, readers, checkpoint / restart
+//   iblb_ctx.hip   lifecycle, state, Lagrangian points, readers, point sampling and tracers, checkpoint / restart
 //   ctx_step.hip   halo exchange, the one-step / two-step / deep schedules, iblb_step, local and
 //                  RCCL groups, the output gather
 //   ctx_band.hip   the IB band cycle (K iterations per cycle with an owed force every iteration)
@@ -162,6 +162,16 @@ struct iblb_ctx {
     double* red_buf = nullptr;
     size_t red_cap = 0;  // doubles allocated
     std::vector<double> red_host;
+    // passive tracers (iblb_set_tracers): SoA positions in double, wraps in x counted in laps.  tr_n == 0:
+    // none, and iblb_step takes the path it took before there were tracers.  With tracers iblb_step
+    // stops at the iterations tr_next, tr_next + tr_stride, ... and updates them there (tracer_update)
+    double* tr_x = nullptr;
+    double* tr_y = nullptr;
+    int* tr_laps = nullptr;
+    long long tr_n = 0;
+    int tr_stride = 1;
+    long long tr_next = 0;     // the iteration after which the next update runs
+    long long tr_updates = 0;  // updates done since iblb_set_tracers
     // state machine
     int phase = iblbh::PH_EMPTY;
     long long t = 0;
@@ -343,6 +353,7 @@ int check_wait_err(iblb_ctx* c);  // after a synchronize: did an edge wave's wai
 int set_wait_ticks(iblb_ctx* c);  // wait_ticks from wait_timeout_s and the device's wall-clock rate
 int hold_release(iblb_ctx* c);    // join the test hold's host thread (IBLB_TEST_HOLD)
 int prepare_read(iblb_ctx* c);
+int tracer_update(iblb_ctx* c);  // iblb_ctx.hip: one update of the tracers from the current state (no host synchronise)
 int free_boot(iblb_ctx* c);
 int alloc_zero(iblb_ctx* c, void** p, size_t bytes);
 int run_cilia(iblb_ctx* c);

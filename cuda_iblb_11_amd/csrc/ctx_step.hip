@@ -696,12 +696,9 @@ static int step_range(iblb_ctx* c, int nsteps) {
     return IBLB_OK;
 }
 
-int iblb_step(iblb_ctx* c, int nsteps) {
-    if (!c || nsteps < 0) return IBLB_ERR_ARG;
-    if (c->transport == TR_LOCAL) return fail(c, IBLB_ERR_STATE, "local group: use iblb_group_step");
-    int rc = check_ready(c);
-    if (rc) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
+// nsteps iterations as one call schedules them; the band streams may still run at the end
+static int step_call(iblb_ctx* c, int nsteps) {
+    int rc;
     const int K = c->sweep_depth;
     // on-device cilia: the kinematics of up to CILIA_AHEAD iterations run ahead as a schedule, so
     // that the band cycle applies (cilia_schedule); otherwise one kinematics launch per iteration
@@ -715,6 +712,30 @@ int iblb_step(iblb_ctx* c, int nsteps) {
             return rc;
         }
         done += seg;
+    }
+    return IBLB_OK;
+}
+
+int iblb_step(iblb_ctx* c, int nsteps) {
+    if (!c || nsteps < 0) return IBLB_ERR_ARG;
+    if (c->transport == TR_LOCAL) return fail(c, IBLB_ERR_STATE, "local group: use iblb_group_step");
+    int rc = check_ready(c);
+    if (rc) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->tr_n == 0) {
+        if ((rc = step_call(c, nsteps))) return rc;
+    } else {
+        // passive tracers: the call is cut at their update iterations; each piece (at most tr_stride
+        // iterations) is scheduled as a call of its own, then the tracers move with that state held
+        // fixed, as if the caller had stepped the piece, sampled u and updated them
+        for (int done = 0; done < nsteps;) {
+            const long long to_update = c->tr_next - c->t;
+            if (to_update < 1) return fail(c, IBLB_ERR_STATE, "tracers: the next update iteration is not ahead of the state");
+            const int piece = (int)std::min<long long>(nsteps - done, to_update);
+            if ((rc = step_call(c, piece))) return rc;
+            done += piece;
+            if (c->t == c->tr_next && (rc = tracer_update(c))) return rc;
+        }
     }
     if ((rc = band_join(c))) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));

@@ -1,5 +1,5 @@
 // iblb_ctx.hip — the fused context API of include/iblb.h: lifecycle, state, Lagrangian points,
-// readers in the reference layouts, the output gather and checkpoint / restart.  Time stepping is
+// readers in the reference layouts, point sampling and passive tracers, the output gather and checkpoint / restart.  Time stepping is
 // in ctx_step.hip, the IB band cycle in ctx_band.hip; the context itself in ctx.h.
 #include <cmath>
 #include <cstdio>
@@ -462,7 +462,7 @@ void iblb_destroy(iblb_ctx* c) {
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     void* bufs[] = {c->g_alloc, c->cil_samples, c->cil_lasts, c->cil_bpoints, c->rho0, c->u0, c->force0, c->d_s,
                     c->d_us, c->d_Fs, c->d_eps, c->d_Fs_sum, c->fd_alloc, c->fl_alloc, c->d_Q, c->red_buf, c->d_sch_s,
-                    c->d_sch_us, c->d_sch_eps};
+                    c->d_sch_us, c->d_sch_eps, c->tr_x, c->tr_y, c->tr_laps};
     for (void* p : bufs)
         if (p) (void)hipFree(p);
     if (c->sig) (void)hipFree(c->sig);
@@ -536,6 +536,7 @@ int iblb_set_state(iblb_ctx* c, const double* rho, const double* u, const double
     c->ib_state = IB_NONE;
     c->ghost = 0;
     c->bnd_w = INT_MAX;
+    if (c->tr_n > 0) c->tr_next = c->tr_stride;  // the tracers stay; their updates count from the new state
     return IBLB_OK;
 }
 
@@ -1052,6 +1053,154 @@ int iblb_gather_macro(iblb_ctx* c, int root, double* rho, double* u) {
 
 }  // extern "C"
 
+// ---- point sampling and passive tracers -------------------------------------------------------------
+namespace iblbh {
+
+// The state-dependent part of the kernels' arguments (no window): what window_args gives every reader
+static FieldsArgs point_args(iblb_ctx* c, unsigned fields) {
+    return window_args(c, iblb_window{0, 0, 1, 1, 1, 1}, 0, 1, fields);
+}
+
+// Every position finite and inside [0, XDIM) x [0, YDIM-1]: the kernels index the lattice from them
+static int check_positions(iblb_ctx* c, long long n, const double* x, const double* y) {
+    if (c->ny < 2) return fail(c, IBLB_ERR_ARG, "bilinear sampling needs YDIM >= 2");
+    const double X = (double)c->nx, ytop = (double)(c->ny - 1);
+    for (long long p = 0; p < n; ++p)
+        if (!(std::isfinite(x[p]) && std::isfinite(y[p]) && x[p] >= 0. && x[p] < X && y[p] >= 0. && y[p] <= ytop))
+            return fail(c, IBLB_ERR_ARG,
+                        "point " + std::to_string(p) + " is non-finite or outside 0 <= x < XDIM, 0 <= y <= YDIM-1");
+    return IBLB_OK;
+}
+
+static int group_refused(iblb_ctx* c, const char* what) {
+    return fail(c, IBLB_ERR_UNSUPPORTED,
+                std::string(what) + ": a lone slab only (the four cells of a point may straddle the slabs of a group)");
+}
+
+static void tracers_free(iblb_ctx* c) {
+    for (void* p : {(void*)c->tr_x, (void*)c->tr_y, (void*)c->tr_laps})
+        if (p) (void)hipFree(p);
+    c->tr_x = c->tr_y = nullptr;
+    c->tr_laps = nullptr;
+    c->tr_n = 0;
+    c->tr_stride = 1;
+    c->tr_next = 0;
+    c->tr_updates = 0;
+}
+
+// One update of the tracers from the current state, on the context's stream: the state prepared as
+// for a reader (the band streams joined, the owed IB force evaluated), then one launch.
+int tracer_update(iblb_ctx* c) {
+    int rc = band_join(c);
+    if (rc || (rc = prepare_read(c))) return rc;
+    const FieldsArgs a = point_args(c, IBLB_FIELD_UX | IBLB_FIELD_UY);
+    if (is_f64(c))
+        HIP_TRY(c, launch_tracer_advect<double>(gptr<double>(c, c->cur), c->L, halo_of<double>(c, c->cur), a, (long)c->tr_n,
+                                                c->tr_stride, c->tr_x, c->tr_y, c->tr_laps, c->stream));
+    else
+        HIP_TRY(c, launch_tracer_advect<float>(gptr<float>(c, c->cur), c->L, halo_of<float>(c, c->cur), a, (long)c->tr_n,
+                                               c->tr_stride, c->tr_x, c->tr_y, c->tr_laps, c->stream));
+    c->tr_next += c->tr_stride;
+    c->tr_updates++;
+    return IBLB_OK;
+}
+
+}  // namespace iblbh
+
+extern "C" {
+
+int iblb_sample_points(iblb_ctx* c, int n, const double* x, const double* y, unsigned fields, double* out) {
+    if (!c) return IBLB_ERR_ARG;
+    const unsigned known = IBLB_FIELD_RHO | IBLB_FIELD_UX | IBLB_FIELD_UY | IBLB_FIELD_VORT | IBLB_FIELD_SXX |
+                           IBLB_FIELD_SXY | IBLB_FIELD_SYY;
+    if (n < 0) return fail(c, IBLB_ERR_ARG, "n is negative");
+    if (n > 0 && (!x || !y || !out)) return fail(c, IBLB_ERR_ARG, "x, y or out is NULL");
+    if (fields == 0 || (fields & ~known)) return fail(c, IBLB_ERR_ARG, "fields: no field or an unknown IBLB_FIELD_* bit");
+    if (!single_slab(c)) return group_refused(c, "iblb_sample_points");
+    int rc = check_positions(c, n, x, y);
+    if (rc) return rc;
+    if (n == 0) return IBLB_OK;
+    if ((rc = prepare_read(c))) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int nf = __builtin_popcount(fields);
+    const size_t np = (size_t)n;
+    std::vector<double> xy(2 * np);  // one copy in: x then y
+    std::copy(x, x + np, xy.begin());
+    std::copy(y, y + np, xy.begin() + np);
+    DevBuf d_xy, d_out;
+    HIP_TRY(c, hipMalloc(&d_xy.p, 2 * np * sizeof(double)));
+    HIP_TRY(c, hipMalloc(&d_out.p, nf * np * sizeof(double)));
+    HIP_TRY(c, hipMemcpyAsync(d_xy.p, xy.data(), 2 * np * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    const FieldsArgs a = point_args(c, fields);
+    if (is_f64(c))
+        HIP_TRY(c, launch_sample_points<double>(gptr<double>(c, c->cur), c->L, halo_of<double>(c, c->cur), a, (long)n,
+                                                (const double*)d_xy.p, (double*)d_out.p, c->stream));
+    else
+        HIP_TRY(c, launch_sample_points<float>(gptr<float>(c, c->cur), c->L, halo_of<float>(c, c->cur), a, (long)n,
+                                               (const double*)d_xy.p, (double*)d_out.p, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(out, d_out.p, nf * np * sizeof(double), hipMemcpyDeviceToHost));
+    return IBLB_OK;
+}
+
+int iblb_set_tracers(iblb_ctx* c, long long n, const double* x, const double* y, int stride) {
+    if (!c) return IBLB_ERR_ARG;
+    if (n < 0) return fail(c, IBLB_ERR_ARG, "n is negative");
+    if (stride < 1) return fail(c, IBLB_ERR_ARG, "stride must be >= 1");
+    if (n > 0 && (!x || !y)) return fail(c, IBLB_ERR_ARG, "x or y is NULL");
+    if (!single_slab(c)) return group_refused(c, "iblb_set_tracers");
+    int rc = check_positions(c, n, x, y);
+    if (rc) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (n == 0) {
+        tracers_free(c);
+        return IBLB_OK;
+    }
+    // the new arrays first: a failed allocation leaves the previous tracers as they were
+    const size_t np = (size_t)n;
+    DevBuf dx, dy, dl;
+    HIP_TRY(c, hipMalloc(&dx.p, np * sizeof(double)));
+    HIP_TRY(c, hipMalloc(&dy.p, np * sizeof(double)));
+    HIP_TRY(c, hipMalloc(&dl.p, np * sizeof(int)));
+    HIP_TRY(c, hipMemcpy(dx.p, x, np * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(dy.p, y, np * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemsetAsync(dl.p, 0, np * sizeof(int), c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    tracers_free(c);
+    c->tr_x = (double*)dx.p;
+    c->tr_y = (double*)dy.p;
+    c->tr_laps = (int*)dl.p;
+    dx.p = dy.p = dl.p = nullptr;
+    c->tr_n = n;
+    c->tr_stride = stride;
+    c->tr_next = c->t + stride;
+    c->tr_updates = 0;
+    return IBLB_OK;
+}
+
+int iblb_get_tracers(iblb_ctx* c, double* x, double* y, int* laps) {
+    if (!c) return IBLB_ERR_ARG;
+    if (c->tr_n == 0) return IBLB_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const size_t np = (size_t)c->tr_n;
+    if (x) HIP_TRY(c, hipMemcpy(x, c->tr_x, np * sizeof(double), hipMemcpyDeviceToHost));
+    if (y) HIP_TRY(c, hipMemcpy(y, c->tr_y, np * sizeof(double), hipMemcpyDeviceToHost));
+    if (laps) HIP_TRY(c, hipMemcpy(laps, c->tr_laps, np * sizeof(int), hipMemcpyDeviceToHost));
+    return IBLB_OK;
+}
+
+int iblb_tracer_count(iblb_ctx* c, long long* n, int* stride, long long* updates) {
+    if (!c) return IBLB_ERR_ARG;
+    if (n) *n = c->tr_n;
+    if (stride) *stride = c->tr_stride;
+    if (updates) *updates = c->tr_updates;
+    return IBLB_OK;
+}
+
+}  // extern "C"
+
 // ---- checkpoint / restart -------------------------------------------------------------------------
 // File: 8-byte magic, 12 int64 fields, 6 doubles, then the stored populations g (plane i, column
 // xc, rows y; storage precision, no padding), the Lagrangian points and the cilia buffers.
@@ -1166,6 +1315,7 @@ int iblb_load_checkpoint(iblb_ctx* c, const char* path) {
     // cilia configuration first (allocates its buffers), then every array
     c->ib_state = IB_NONE;
     c->phase = PH_EMPTY;
+    tracers_free(c);  // a checkpoint holds no tracers (the caller saves them with iblb_get_tracers)
     if (iv[CK_CILIA]) {
         iblb_cilia k{(int)iv[CK_CNUM], dv[CK_CSPACE], (int)iv[CK_CT], (int)iv[CK_CPSTEP]};
         if ((rc = iblb_set_cilia(c, &k))) return rc;

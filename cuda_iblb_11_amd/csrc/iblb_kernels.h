@@ -233,6 +233,19 @@ template <typename T>
 hipError_t launch_reduce_fields(const T* g, Layout L, Halo<T> H, const FieldsArgs& a, const ReduceGeom& q,
                                 double* scratch, hipStream_t s);
 
+// Point sampling and passive tracers (tracer_kernels.hip; include/iblb.h iblb_sample_points, iblb_set_tracers):
+// one lane per point, its four cells evaluated by the device functions of field_eval.h.  Of FieldsArgs the
+// window members are unused (fields, the force, the boot arrays and kvisc apply).  A lone slab only: the
+// cells of a point wrap modulo ncol.
+// out[k*n + p]: the k-th set bit of a.fields at the point (xy[p], xy[n + p]).
+template <typename T>
+hipError_t launch_sample_points(const T* g, Layout L, Halo<T> H, const FieldsArgs& a, long n, const double* xy,
+                                double* out, hipStream_t s);
+// One explicit-Euler update of n tracers over `stride` iterations with the state held fixed.
+template <typename T>
+hipError_t launch_tracer_advect(const T* g, Layout L, Halo<T> H, const FieldsArgs& a, long n, int stride, double* x,
+                                double* y, int* laps, hipStream_t s);
+
 // q(u^t) of the current state for the flux column (added to *out).
 template <typename T>
 hipError_t launch_flux(const T* g, Layout L, Halo<T> H, const double* fdense, long fplane,

@@ -1,0 +1,146 @@
+// tracer_kernels.hip — the Lagrangian side of the readers (include/iblb.h): bilinear sampling of the
+// fields at arbitrary points (iblb_sample_points) and the explicit-Euler update of the context's passive
+// tracers (iblb_set_tracers; launched by iblb_step at the update iterations).
+//
+// One lane = one point.  Lanes run along the point index: the positions are SoA doubles, read and
+// written coalesced; the four cells of a point are a gather (9 population loads each, 45 with
+// vorticity), served by the caches where neighbouring points share cells.  No atomics, no cross-lane
+// steps: every output value is a function of its own point and the state.  Each of the four cells is
+// evaluated by the device functions of field_eval.h, so a cell's value has the bits iblb_get_fields
+// returns for it; the interpolation is the header's expression, one rounding per operation.
+#include "field_eval.h"
+
+namespace iblb {
+
+// The four cells and the two weights of a position (include/iblb.h iblb_sample_points).  The host
+// validates every position it copies in and the update rule stores only positions in range; the
+// indices are clamped to the lattice all the same, so that no position, whatever its value, forms an
+// index outside the buffers (for a position in range the clamps change nothing).
+struct Bilinear {
+    int i0, i1, j0, j1;
+    double a, b;
+};
+
+__device__ __forceinline__ Bilinear bilinear_of(double x, double y, int ncol, int ny) {
+#pragma clang fp contract(off)
+    Bilinear q;
+    const double fx = floor(x), fy = floor(y);
+    int i0 = fx >= 0. ? (fx < (double)ncol ? (int)fx : ncol - 1) : 0;  // (a NaN compares false: column 0)
+    int j0 = fy >= 0. ? (fy < (double)(ny - 1) ? (int)fy : ny - 2) : 0;
+    q.i0 = i0;
+    q.i1 = i0 + 1 < ncol ? i0 + 1 : 0;
+    q.j0 = j0;
+    q.j1 = j0 + 1;
+    q.a = x - fx;
+    q.b = y - (double)j0;
+    return q;
+}
+
+__device__ __forceinline__ double bilinear_mix(const Bilinear& q, double v00, double v10, double v01, double v11) {
+#pragma clang fp contract(off)
+    return (1.0 - q.b) * ((1.0 - q.a) * v00 + q.a * v10) + q.b * ((1.0 - q.a) * v01 + q.a * v11);
+}
+
+// The selected fields of cell (xc, y), in the order of the IBLB_FIELD_* bits, as fields_out_kernel
+// (field_kernels.hip) evaluates them
+template <typename T>
+__device__ __forceinline__ void cell_fields(const T* __restrict__ g, const Layout& L, const Halo<T>& H,
+                                            const FieldsArgs& a, int xc, int y, double v[7]) {
+#pragma clang fp contract(off)
+    double f[9], r, ux, uy;
+    cell_state<T>(g, L, H, a, xc, y, f, r, ux, uy);
+    v[0] = r;
+    v[1] = ux;
+    v[2] = uy;
+    v[3] = (a.fields & IBLB_FIELD_VORT) ? cell_vorticity<T>(g, L, H, a, xc, y, ux) : 0.;
+    v[4] = v[5] = v[6] = 0.;
+    if (a.fields & (IBLB_FIELD_SXX | IBLB_FIELD_SXY | IBLB_FIELD_SYY)) cell_stress(f, r, ux, uy, a.kvisc, v[4], v[5], v[6]);
+}
+
+// out[k*n + p]: the k-th set bit of a.fields at point p = (xy[p], xy[n + p])
+template <typename T>
+__global__ __launch_bounds__(256) void sample_points_kernel(const T* __restrict__ g, Layout L, Halo<T> H, FieldsArgs a,
+                                                            long n, const double* __restrict__ xy,
+                                                            double* __restrict__ out) {
+#pragma clang fp contract(off)
+    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const Bilinear q = bilinear_of(xy[p], xy[n + p], L.ncol, L.ny);
+    double v00[7], v10[7], v01[7], v11[7];
+    cell_fields<T>(g, L, H, a, q.i0, q.j0, v00);
+    cell_fields<T>(g, L, H, a, q.i1, q.j0, v10);
+    cell_fields<T>(g, L, H, a, q.i0, q.j1, v01);
+    cell_fields<T>(g, L, H, a, q.i1, q.j1, v11);
+    double* o = out + p;
+#pragma unroll
+    for (int k = 0; k < 7; ++k)
+        if (a.fields & (1u << k)) {
+            *o = bilinear_mix(q, v00[k], v10[k], v01[k], v11[k]);
+            o += n;
+        }
+}
+
+// One explicit-Euler update of the tracers with the state held fixed (include/iblb.h iblb_set_tracers):
+// x += stride * ux(x, y), y += stride * uy(x, y); x wraps periodically (laps counts the wraps), y is
+// clamped to the walls' rows.  A stored position stays finite and in range.
+template <typename T>
+__global__ __launch_bounds__(256) void tracer_advect_kernel(const T* __restrict__ g, Layout L, Halo<T> H, FieldsArgs a,
+                                                            long n, double stride, double* __restrict__ x,
+                                                            double* __restrict__ y, int* __restrict__ laps) {
+#pragma clang fp contract(off)
+    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const double xp = x[p], yp = y[p];
+    const Bilinear q = bilinear_of(xp, yp, L.ncol, L.ny);
+    double f[9], r, ux00, uy00, ux10, uy10, ux01, uy01, ux11, uy11;
+    cell_state<T>(g, L, H, a, q.i0, q.j0, f, r, ux00, uy00);
+    cell_state<T>(g, L, H, a, q.i1, q.j0, f, r, ux10, uy10);
+    cell_state<T>(g, L, H, a, q.i0, q.j1, f, r, ux01, uy01);
+    cell_state<T>(g, L, H, a, q.i1, q.j1, f, r, ux11, uy11);
+    const double ux = bilinear_mix(q, ux00, ux10, ux01, ux11);
+    const double uy = bilinear_mix(q, uy00, uy10, uy01, uy11);
+    if (!(isfinite(ux) && isfinite(uy))) return;  // the tracer keeps its position
+    const double X = (double)L.ncol, ytop = (double)(L.ny - 1);
+    double xn = xp + stride * ux, yn = yp + stride * uy;
+    int lp = laps[p];
+    if (xn >= X) {
+        xn -= X;
+        lp += 1;
+    } else if (xn < 0.) {
+        xn += X;
+        lp -= 1;
+    }
+    if (xn >= 0. && xn < X) {  // else more than one lattice length in one update: x and laps stay
+        x[p] = xn;
+        laps[p] = lp;
+    }
+    yn = yn < 0. ? 0. : (yn > ytop ? ytop : yn);
+    y[p] = yn;
+}
+
+template <typename T>
+hipError_t launch_sample_points(const T* g, Layout L, Halo<T> H, const FieldsArgs& a, long n, const double* xy,
+                                double* out, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    sample_points_kernel<T><<<(unsigned)((n + 255) / 256), 256, 0, s>>>(g, L, H, a, n, xy, out);
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t launch_tracer_advect(const T* g, Layout L, Halo<T> H, const FieldsArgs& a, long n, int stride, double* x,
+                                double* y, int* laps, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    tracer_advect_kernel<T><<<(unsigned)((n + 255) / 256), 256, 0, s>>>(g, L, H, a, n, (double)stride, x, y, laps);
+    return hipGetLastError();
+}
+
+template hipError_t launch_sample_points<double>(const double*, Layout, Halo<double>, const FieldsArgs&, long,
+                                                 const double*, double*, hipStream_t);
+template hipError_t launch_sample_points<float>(const float*, Layout, Halo<float>, const FieldsArgs&, long, const double*,
+                                                double*, hipStream_t);
+template hipError_t launch_tracer_advect<double>(const double*, Layout, Halo<double>, const FieldsArgs&, long, int,
+                                                 double*, double*, int*, hipStream_t);
+template hipError_t launch_tracer_advect<float>(const float*, Layout, Halo<float>, const FieldsArgs&, long, int, double*,
+                                                double*, int*, hipStream_t);
+
+}  // namespace iblb

@@ -344,6 +344,48 @@ class Lattice:
                          row_sum=rs[k] if rows else None, col_sum=cs[k] if cols else None)
                 for k, n in enumerate(order)}
 
+    def sample(self, names, x, y) -> dict:
+        """Fields at arbitrary points, bilinearly interpolated on the device (iblb_sample_points).
+        names as for `fields`; x, y: global lattice coordinates, 0 <= x < nx (periodic), 0 <= y <= ny-1.
+        Returns {name: array [n]} in ascending bit order.  A lone slab only."""
+        names = [names] if isinstance(names, str) else list(names)
+        unknown = [n for n in names if n not in L.FIELDS]
+        if unknown or not names:
+            raise ValueError(f"fields must be chosen from {sorted(L.FIELDS)}, got {names}")
+        x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+        y = np.ascontiguousarray(y, dtype=np.float64).ravel()
+        if x.size != y.size:
+            raise ValueError("x and y must hold the same number of points")
+        order = sorted(set(names), key=L.FIELDS.get)
+        bits = sum(L.FIELDS[n] for n in order)
+        out = np.empty((len(order), x.size))
+        self._check(self._lib.iblb_sample_points(self._h, x.size, _ptr(x), _ptr(y), bits, _ptr(out)))
+        return {n: out[k] for k, n in enumerate(order)}
+
+    # -- passive tracers ----------------------------------------------------------------------
+    def set_tracers(self, x, y, stride: int = 1) -> None:
+        """Tracers at (x, y) that `step` moves with the fluid: one explicit-Euler update every
+        `stride` iterations (iblb_set_tracers).  Empty x, y remove them.  A lone slab only."""
+        x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+        y = np.ascontiguousarray(y, dtype=np.float64).ravel()
+        if x.size != y.size:
+            raise ValueError("x and y must hold the same number of tracers")
+        self._check(self._lib.iblb_set_tracers(self._h, x.size, _ptr(x), _ptr(y), int(stride)))
+
+    def tracer_info(self) -> dict:
+        """{"n", "stride", "updates"} of the tracers (iblb_tracer_count); n == 0: none set."""
+        n, stride, updates = C.c_longlong(0), C.c_int(0), C.c_longlong(0)
+        self._check(self._lib.iblb_tracer_count(self._h, C.byref(n), C.byref(stride), C.byref(updates)))
+        return {"n": n.value, "stride": stride.value, "updates": updates.value}
+
+    def tracers(self) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Current tracers: x [n], y [n] (float64) and laps [n] (int32), the wraps in x counted so
+        that the net x displacement is x - x_start + laps * nx."""
+        n = self.tracer_info()["n"]
+        x, y, laps = np.empty(n), np.empty(n), np.zeros(n, dtype=np.int32)
+        self._check(self._lib.iblb_get_tracers(self._h, _ptr(x), _ptr(y), _ptr(laps)))
+        return x, y, laps
+
     @property
     def steps(self) -> int:
         n = C.c_longlong(0)

@@ -308,6 +308,51 @@ typedef struct iblb_field_stats {
 int iblb_reduce_fields(iblb_ctx* ctx, const iblb_window* w, unsigned fields, iblb_field_stats* stats,
                        double* row_sum, double* col_sum);
 
+/* Point sampling: chosen fields at n arbitrary points, interpolated on the device; the points cross in one
+ * copy and the results return in one.  x, y [n] are host arrays in global lattice coordinates, `fields` the
+ * seven IBLB_FIELD_* bits, out[k*n + p] the k-th set bit (ascending) at point p.  A point needs 0 <= x < XDIM
+ * and 0 <= y <= YDIM-1, both finite.  With
+ *   i0 = floor(x), i1 = (i0 + 1) mod XDIM (periodic), a = x - i0,
+ *   j0 = min(floor(y), YDIM-2), j1 = j0 + 1, b = y - j0  (y = YDIM-1: b = 1 on the top row)
+ * and vIJ the value iblb_get_fields returns for cell (iI, jJ) at that moment, bit for bit,
+ *   v = (1-b)*((1-a)*v00 + a*v10) + b*((1-a)*v01 + a*v11)
+ * in double, one rounding per operation, no contraction.  Valid in every phase, the boot phase included.
+ * n < 0, a NULL pointer with n > 0, fields == 0, an unknown bit, YDIM < 2, or any point out of range or
+ * non-finite: IBLB_ERR_ARG, checked before any launch, no output touched.  n == 0: IBLB_OK.  A slab of a
+ * local or RCCL group: IBLB_ERR_UNSUPPORTED (a point's four cells may straddle slabs). */
+int iblb_sample_points(iblb_ctx* ctx, int n, const double* x, const double* y, unsigned fields, double* out);
+
+/* Passive tracers: n points the context itself moves with the fluid while iblb_step runs, so that following
+ * fluid parcels needs no readback and keeps the deep sweep between their updates.  On the device they are
+ * x[n], y[n] in double and laps[n] in int.  The positions must be double: at x ~ 4096 a float's ulp is 4.9e-4,
+ * more than one iteration's displacement at this project's Mach numbers, so a float position would not move.
+ * iblb_set_tracers validates the positions as iblb_sample_points does, copies them, zeroes laps and
+ * records t0 = iblb_get_step; stride >= 1.  It replaces any previous set; n == 0 removes the tracers, and
+ * iblb_step is then exactly what it is without them.  A slab of a local or RCCL group: IBLB_ERR_UNSUPPORTED.
+ * An error leaves the previous tracers as they were.
+ * Update rule.  After the iterations t0 + stride, t0 + 2 stride, ... the context does one explicit-Euler
+ * update with the state of that iteration held fixed: (ux, uy) = the bilinear sample above of IBLB_FIELD_UX and
+ * IBLB_FIELD_UY at (x, y);  x' = x + (double)stride*ux,  y' = y + (double)stride*uy;  x' >= XDIM: x' -= XDIM,
+ * laps += 1;  x' < 0: x' += XDIM, laps -= 1;  x' still outside [0, XDIM) after that one wrap: x and laps stay
+ * as they were;  y' is clamped to [0, YDIM-1];  a non-finite ux or uy: the tracer keeps its position.  A stored
+ * position is therefore always finite and in range, and a tracer's net x displacement is
+ * x - x_start + laps*XDIM.
+ * iblb_step(nsteps) with tracers cuts the call at the update iterations and schedules each piece (at most
+ * `stride` iterations) as a call of its own; the result is by definition that of the caller doing
+ * iblb_step(piece), sampling u and updating on the host.  Updates count on across calls: with stride 5,
+ * iblb_step(3) then iblb_step(4) update once, after iteration t0 + 5.  A stride >= K (IBLB_SWEEP_DEPTH) keeps
+ * the deep sweep between updates; stride 1 costs the one-step path at every iteration.  One update is one
+ * launch, one lane per tracer, a gather of 36 population loads: tracers ordered like the lattice (y fastest)
+ * share those loads between neighbouring lanes and update several times faster than tracers in random order
+ * (DESIGN.md section 10).
+ * iblb_set_state keeps the tracers (positions, laps and the update count) and re-bases t0 to the new state's
+ * step count 0: the next update follows `stride` iterations later.  Checkpoints do not hold tracers:
+ * iblb_load_checkpoint removes them; the caller saves them with iblb_get_tracers and sets them again. */
+int iblb_set_tracers(iblb_ctx* ctx, long long n, const double* x, const double* y, int stride);
+int iblb_get_tracers(iblb_ctx* ctx, double* x, double* y, int* laps);   /* [n] each; any may be NULL */
+/* Tracers set, their stride and the updates done since iblb_set_tracers (any may be NULL). */
+int iblb_tracer_count(iblb_ctx* ctx, long long* n, int* stride, long long* updates);
+
 /* Timing: when enabled (1) every collide-stream launch is bracketed by HIP events on the
  * stream it runs on; iblb_get_timing() returns the sums (and resets them if reset).  enabled = 2:
  * only the deep (K-iteration) launches are timed, by their own dispatch / completion signals (no
