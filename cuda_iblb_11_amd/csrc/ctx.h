@@ -74,7 +74,7 @@ struct iblb_ctx {
     bool sweep_on = true;       // multi-iteration sweeps (IBLB_SWEEP)
     int sweep_w = 4, sweep_vs = 2;  // two-iteration sweeps: columns per wave, cells per lane
     int sweep_depth = 5;        // K iterations per deep launch (IBLB_SWEEP_DEPTH; 2 = two-step only)
-    int deep_w = 96, deep_vs = 2, deep_balance = 1;  // IBLB_DEEP_W / _VS / _BALANCE
+    int deep_w = 128, deep_vs = 2, deep_balance = 1;  // IBLB_DEEP_W / _VS / _BALANCE
     iblb::DeepBuild deep_build{};  // the deep sweeps' build features (iblb_ctx.hip: the measured default; IBLB_DEEP_BUILD)
     int slab_vs = 1;            // cells per lane of a group slab's deep sweeps
     int reserved_cus = 0, ncu = 0;  // CUs kept free of the compute stream (RCCL groups), device CUs

@@ -359,14 +359,18 @@ int iblb_create(const iblb_config* cfg, iblb_ctx** out) {
     // kernel defaults measured on MI355X: two-step sweeps 16 B per lane
     // (f64 2 cells, f32 4) over 4 / 6 columns; deep sweeps K = 7 (round 4, profiles/r04/depth: M f64
     // 171k / 174k / 182k MLUPS at K = 5 / 6 / 7, f32 255k / 280k / 304k; K = 8 dropped), 2 cells per
-    // lane, ~96 (f64) / ~64
-    // (f32) columns balanced to whole rounds of resident waves, the linear wave order dealt to the
-    // XCDs in contiguous ranges (map 2) with alternate sweeps walking towards each other
+    // lane, ~128 (f64) / ~64 (f32) columns requested, balanced to whole rounds of resident waves, the
+    // linear wave order dealt to the XCDs in contiguous ranges (map 2) with alternate sweeps walking
+    // towards each other.  f64 (one wave per SIMD): 128 makes the tall lattices one round of wider
+    // sweeps instead of two (M: 27 sweeps of 151.7 columns, 999 waves, against 55 of 74.5 columns, 2035
+    // waves: 7 % fewer wave-steps, half the level-1 halo; 208.6-210.3k against 204.0-206.4k MLUPS at 96
+    // in 7 alternating runs, and 128 / 160 / 192 give the same launch, profiles/r07/deep_w).  f32: M
+    // already runs one round of its three waves per SIMD at 64, and a wider request is the same launch.
     c->sweep_on = env_long("IBLB_SWEEP", 1) != 0;
     c->sweep_w = (int)env_long("IBLB_SWEEP_W", f64 ? 4 : 6);
     c->sweep_vs = (int)env_long("IBLB_SWEEP_VS", f64 ? 2 : 4);
     c->sweep_depth = (int)std::min(7L, std::max(2L, env_long("IBLB_SWEEP_DEPTH", 7)));
-    c->deep_w = (int)env_long("IBLB_DEEP_W", f64 ? 96 : 64);
+    c->deep_w = (int)env_long("IBLB_DEEP_W", f64 ? 128 : 64);
     c->deep_vs = (int)env_long("IBLB_DEEP_VS", 2);
     c->deep_build = deep_build;
     c->deep_balance = (int)env_long("IBLB_DEEP_BALANCE", 1);

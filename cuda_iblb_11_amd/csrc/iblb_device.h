@@ -366,6 +366,80 @@ __device__ __forceinline__ R relax_cell(R f[9], const KBase<R>& b, const KForce<
     return ux;
 }
 
+// relax_cell (f64, full populations) on the N cells of a lane with the serial head in lock-step:
+// every operation of the head (pair sums, moments, 1/rho and its Newton steps, u, and collide_sd up
+// to f[0], P, Qa, Rm) is written for cell 0, then for cell 1, ... before the next operation, so that
+// the dependent chain of one cell (about 20 fp64 operations) has the other cell's beside it; the four
+// pairs then follow cell by cell as in collide_sd.  The operations, their operand order and their
+// FMAs are relax_cell's / collide_sd's (explicit here, contraction off: a*a + b*b contracts to
+// fma(a, a, b*b) there), so every cell rounds as in the one-step kernels.  The constants stay scalar
+// operands of scalar statements (as a two-element vector computation the compiler splats them into
+// vector registers and spills: 295 SGPR spills against 131).
+template <int N>
+__device__ __forceinline__ void relax_cells(double (&f)[N][9], const KBase<double>& b, const KForce<double>& k,
+                                            double (&ux)[N]) {
+#pragma clang fp contract(off)
+#define IBLB_EACH _Pragma("unroll") for (int e = 0; e < N; ++e)
+    double s[N][4], d[N][4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        IBLB_EACH s[e][p] = f[e][pair_a(p)] + f[e][pair_b(p)];
+        IBLB_EACH d[e][p] = f[e][pair_a(p)] - f[e][pair_b(p)];
+    }
+    double t0[N], t1[N], rho[N], mx[N], my[N], inv[N], nr[N], jx[N], jy[N], uy[N];
+    IBLB_EACH t0[e] = s[e][0] + s[e][1];
+    IBLB_EACH t1[e] = s[e][2] + s[e][3];
+    IBLB_EACH t0[e] = t0[e] + t1[e];
+    IBLB_EACH rho[e] = f[e][0] + t0[e];
+    IBLB_EACH inv[e] = __builtin_amdgcn_rcp(rho[e]);
+    // every v_rcp_f64 issued before any cell's Newton step (the scheduler otherwise starts cell 0's
+    // in a few of the levels): no vector ALU instruction crosses; scalar, memory and LDS ones may
+    __builtin_amdgcn_sched_barrier(0x3f4);
+    IBLB_EACH mx[e] = d[e][2] - d[e][3];
+    IBLB_EACH my[e] = d[e][2] + d[e][3];
+    IBLB_EACH mx[e] = d[e][0] + mx[e];
+    IBLB_EACH my[e] = d[e][1] + my[e];
+    IBLB_EACH nr[e] = __builtin_fma(-rho[e], inv[e], 1.0);  // (recip's two Newton steps)
+    IBLB_EACH inv[e] = __builtin_fma(inv[e], nr[e], inv[e]);
+    IBLB_EACH jx[e] = mx[e] + k.hFx;
+    IBLB_EACH jy[e] = my[e] + k.hFy;
+    IBLB_EACH nr[e] = __builtin_fma(-rho[e], inv[e], 1.0);
+    IBLB_EACH inv[e] = __builtin_fma(inv[e], nr[e], inv[e]);
+    IBLB_EACH ux[e] = jx[e] * inv[e];
+    IBLB_EACH uy[e] = jy[e] * inv[e];
+    double usq[N], uF[N], rb[N], P[N][2], Qa[N][2], Rm[N][2];
+    IBLB_EACH usq[e] = uy[e] * uy[e];
+    IBLB_EACH uF[e] = uy[e] * k.Fy;
+    IBLB_EACH usq[e] = __builtin_fma(ux[e], ux[e], usq[e]);
+    IBLB_EACH uF[e] = __builtin_fma(ux[e], k.Fx, uF[e]);
+    IBLB_EACH rb[e] = -usq[e] * b.a1;
+    IBLB_EACH rb[e] = 1.0 + rb[e];
+    IBLB_EACH rb[e] = rho[e] * rb[e];
+    IBLB_EACH t0[e] = rb[e] * b.opw0;
+    IBLB_EACH f[e][0] = __builtin_fma(b.omp, f[e][0], t0[e]);
+#pragma unroll
+    for (int cl = 0; cl < 2; ++cl) {
+        IBLB_EACH t0[e] = uF[e] * b.nck[cl];
+        IBLB_EACH P[e][cl] = __builtin_fma(rb[e], b.opw[cl], t0[e]);
+        IBLB_EACH Qa[e][cl] = rho[e] * b.oqa[cl];
+        IBLB_EACH Rm[e][cl] = rho[e] * b.omwi2[cl];
+    }
+    IBLB_EACH {
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const int cl = p < 2 ? 0 : 1;
+            const double cu = p == 0 ? ux[e] : (p == 1 ? uy[e] : (p == 2 ? ux[e] + uy[e] : uy[e] - ux[e]));
+            const double E = __builtin_fma(cu, __builtin_fma(Qa[e][cl], cu, k.hE[p]), P[e][cl]);
+            const double O = __builtin_fma(Rm[e][cl], cu, k.gO[p]);
+            const double A = __builtin_fma(s[e][p], b.hs, E);
+            const double B = __builtin_fma(d[e][p], b.hd, O);
+            f[e][pair_a(p)] = A + B;
+            f[e][pair_b(p)] = A - B;
+        }
+    }
+#undef IBLB_EACH
+}
+
 // Collide constants of both compute types, folded once on the host (kernel arguments)
 struct KConst {
     KBase<double> bd;

@@ -541,6 +541,37 @@ __device__ __forceinline__ void relax_pair(const T (&s)[9][VS], const Sweep2Args
     }
 }
 
+// f64, two cells per lane, LDS window (the inner walks of the default build): the serial head of both
+// cells' collides in lock-step (relax_cells).  relax_cell twice is emitted cell after cell: two serial
+// heads of ~20 dependent operations per level in the SIMD's only wave.  Side by side they are worth
+// ~1 % on M f64 at the one-round sweep width (212.0-214.4k against 209.4-211.2k MLUPS) and cost 1 % at
+// two rounds; interleaving the pairs as well adds nothing.
+// The other f64 builds keep relax_cell: the band cycle's deep sweep (no window, 398 registers) and the
+// one-cell wall walks.
+template <typename T, int VS, int MODE>
+constexpr bool lockstep_pair() { return sizeof(T) == 8 && VS == 2 && (MODE & MODE_LDSWIN); }
+template <typename T, int VS>
+__device__ __forceinline__ void relax_lockstep(const T (&s)[9][VS], const Sweep2Args<T>& a, bool flux, int fown,
+                                               double& q, T (&out)[9][VS]) {
+    double f[VS][9], ux[VS];
+#pragma unroll
+    for (int k = 0; k < 9; ++k)
+#pragma unroll
+        for (int e = 0; e < VS; ++e) f[e][k] = (double)s[k][e];
+    relax_cells<VS>(f, kbase<double>(a.k), kbody<double>(a.k), ux);
+    if (flux) {  // wave-uniform branch; the lane condition as a select (no exec-mask branch)
+#pragma unroll
+        for (int e = 0; e < VS; ++e) {
+            const double t = ux[e] / a.flux_norm;
+            q += ((fown >> e) & 1) ? t : 0.;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k)
+#pragma unroll
+        for (int e = 0; e < VS; ++e) out[k][e] = (T)f[e][k];
+}
+
 // one column of level l+1 from a window of level l (A = older, B = middle, C = newer column in
 // walking direction DX): the output is B's column; flux: add u_x of the owned rows to q
 // ASH: A's populations that wait in the LDS window arrive already at their pull's rows
@@ -565,6 +596,10 @@ __device__ __forceinline__ void level_from_window(const T (&A)[9][VS], const T (
     }
     if constexpr (packed_pair<T, VS, MODE>()) {
         relax_pair<T, VS>(s, a, flux, fown, q, out);
+        return;
+    }
+    if constexpr (lockstep_pair<T, VS, MODE>()) {
+        relax_lockstep<T, VS>(s, a, flux, fown, q, out);
         return;
     }
 #pragma unroll
@@ -620,6 +655,10 @@ __device__ __forceinline__ void level_from_raw(const Raw<T, VS>& cur, const Swee
     }
     if constexpr (packed_pair<T, VS, MODE>()) {
         relax_pair<T, VS>(s, a, flux, fown, q, out);
+        return;
+    }
+    if constexpr (lockstep_pair<T, VS, MODE>()) {
+        relax_lockstep<T, VS>(s, a, flux, fown, q, out);
         return;
     }
 #pragma unroll
