@@ -86,6 +86,9 @@ class Window(C.Structure):
 FIELDS = {"rho": 1, "ux": 2, "uy": 4, "vort": 8, "sxx": 16, "sxy": 32, "syy": 64}
 # what iblb_reduce_fields accepts: the fields and the reduce-only IBLB_QTY_* bits, in ascending bit order
 QUANTITIES = {**FIELDS, "momx": 128, "momy": 256, "ke": 512, "usq": 1024}
+# flags of iblb_set_average
+AVG_SQ = 1
+AVG_UXUY = 2
 
 
 class FieldStats(C.Structure):
@@ -140,6 +143,11 @@ _SIGS = {
     "iblb_set_tracers": ([_vp, C.c_longlong, _vp, _vp, C.c_int], C.c_int),
     "iblb_get_tracers": ([_vp, _vp, _vp, _vp], C.c_int),
     "iblb_tracer_count": ([_vp, C.POINTER(C.c_longlong), C.POINTER(C.c_int), C.POINTER(C.c_longlong)], C.c_int),
+    "iblb_set_average": ([_vp, C.POINTER(Window), C.c_uint, C.c_int, C.c_int, C.c_uint], C.c_int),
+    "iblb_reset_average": ([_vp], C.c_int),
+    "iblb_get_average": ([_vp, C.c_int, _vp, _vp, _vp, C.POINTER(C.c_longlong)], C.c_int),
+    "iblb_average_info": ([_vp, C.POINTER(Window), C.POINTER(C.c_uint), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                           C.POINTER(C.c_uint), C.POINTER(C.c_longlong)], C.c_int),
     "iblb_set_profiling": ([_vp, C.c_int], C.c_int),
     "iblb_get_timing": ([_vp, C.POINTER(Timing), C.c_int], C.c_int),
     "iblb_get_timing_ex": ([_vp, C.POINTER(Timing), C.c_ulong, C.c_int], C.c_int),

@@ -27,6 +27,14 @@
 // x = (i + 0.5) XDIM / nx_t, y = (j + 0.5) (YDIM - 1) / ny_t, tracer i * ny_t + j, updated every `stride` (default 1)
 // iterations, and writes <it>-tracers.dat beside the fluid files at every output iteration (BigData or not): one line
 // x  y  laps per tracer, lattice units, %.17g.  Checkpoints hold no tracers: a restarted run seeds the grid again.
+// IBLB_AVERAGE=stride[,nbins[,sx[,sy]]] (one GPU) lets the context average rho, u_x, u_y, their squares and u_x u_y
+// (iblb_set_average) on every sx-th column and sy-th row (default 1) of the whole lattice, one sample every `stride`
+// iterations, sample m into bin m % nbins (default 1 bin).  At every output iteration after the run's first it writes
+// <it>-mean.dat beside the fluid files (BigData or not), one line per bin and sample, lattice units, %.17g:
+// bin  x  y  n  mean_rho  mean_ux  mean_uy  var_ux  var_uy  cov_uxuy   with mean = sum/n, var = sum_sq/n - mean^2,
+// cov = sum_uxuy/n - mean_ux mean_uy; a blank line after each window row; a bin with n == 0 writes nothing.  It then
+// calls iblb_reset_average: each file is the average over the preceding output interval (the first file: from the
+// run's first iteration).  Checkpoints hold no averages: a restarted run starts them again.
 #include <sys/stat.h>
 #include <sys/time.h>
 #include <unistd.h>
@@ -212,6 +220,37 @@ int main(int argc, char* argv[]) {
         }
     }
 
+    // time- and phase-averaged fields (extension): sample stride, 0 = off
+    int av_stride = 0, av_nbins = 1, av_sx = 1, av_sy = 1;
+    if (const char* as = getenv("IBLB_AVERAGE"); as && *as) {
+        // one to four integers >= 1 separated by commas, nothing else
+        int* const dst[4] = {&av_stride, &av_nbins, &av_sx, &av_sy};
+        bool ok = true;
+        int n = 0;
+        for (const char* p = as; ok; ++n) {
+            char* end = nullptr;
+            errno = 0;
+            const long v = strtol(p, &end, 10);
+            ok = n < 4 && *p >= '0' && *p <= '9' && errno == 0 && v >= 1 && v <= 1000000000L &&
+                 (*end == ',' || *end == 0);
+            if (!ok) break;
+            *dst[n] = (int)v;
+            if (*end == 0) {
+                ++n;
+                break;
+            }
+            p = end + 1;
+        }
+        if (!ok || n < 1) {
+            if (lead) cerr << "IBLB_AVERAGE must be stride[,nbins[,sx[,sy]]] with every value >= 1, got " << as << endl;
+            return 2;
+        }
+        if (world > 1) {  // averaging on the slabs of a group is not built: a lone slab only (include/iblb.h)
+            if (lead) cerr << "IBLB_AVERAGE is not available under a launcher (WORLD_SIZE > 1): run on one GPU" << endl;
+            return 2;
+        }
+    }
+
     const double dx = 1. / LENGTH;
     const double dt = 1. / (T);
     const double SPEED = 0.8 * 1000 / T;
@@ -294,6 +333,16 @@ int main(int argc, char* argv[]) {
         if ((rc = iblb_set_tracers(ctx, (long long)tr_n, tr_x.data(), tr_y.data(), tr_stride)))
             return die(ctx, rc, "iblb_set_tracers");
     }
+    // averaged fields: rho, u_x, u_y with their squares and u_x u_y on every av_sx-th column and av_sy-th row,
+    // from the run's first iteration (a restarted run's too: checkpoints hold no averages)
+    iblb_window av_win{0, 0, ((int)XDIM - 1) / av_sx + 1, ((int)YDIM - 1) / av_sy + 1, av_sx, av_sy};
+    const size_t av_np = av_stride > 0 ? (size_t)av_win.nx * av_win.ny : 0;
+    std::vector<double> av_sum(3 * av_np), av_sq(3 * av_np), av_xy(av_np);
+    bool av_first = true;  // the first output iteration writes no mean file
+    if (av_stride > 0 &&
+        (rc = iblb_set_average(ctx, &av_win, IBLB_FIELD_RHO | IBLB_FIELD_UX | IBLB_FIELD_UY, av_stride, av_nbins,
+                               IBLB_AVG_SQ | IBLB_AVG_UXUY)))
+        return die(ctx, rc, "iblb_set_average");
 
     //----------------------------------------DEFINE DIRECTORIES---------------------------------- (main.cu:589-631)
     std::string output_data = env_str("IBLB_DATA_DIR", "Data/");
@@ -468,6 +517,34 @@ int main(int argc, char* argv[]) {
                 for (size_t k = 0; k < tr_n; k++) fprintf(ft, "%.17g\t%.17g\t%d\n", tr_x[k], tr_y[k], tr_laps[k]);
                 fclose(ft);
             }
+            if (av_stride > 0 && !av_first) {
+                outfile = raw_data + to_string(it) + "-mean.dat";
+                FILE* fm = fopen(outfile.c_str(), "w");
+                if (!fm) {
+                    fprintf(stderr, "cannot write %s: %s\n", outfile.c_str(), strerror(errno));
+                    return 1;
+                }
+                for (int b = 0; b < av_nbins; b++) {
+                    long long n = 0;
+                    if ((rc = iblb_get_average(ctx, b, av_sum.data(), av_sq.data(), av_xy.data(), &n)))
+                        return die(ctx, rc, "iblb_get_average");
+                    if (n == 0) continue;
+                    const double dn = (double)n;
+                    for (int j = 0; j < av_win.ny; j++) {
+                        for (int i = 0; i < av_win.nx; i++) {
+                            const size_t k = (size_t)j * av_win.nx + i;
+                            const double mr = av_sum[k] / dn, mx = av_sum[av_np + k] / dn, my = av_sum[2 * av_np + k] / dn;
+                            fprintf(fm, "%d\t%d\t%d\t%lld\t%.17g\t%.17g\t%.17g\t%.17g\t%.17g\t%.17g\n", b, i * av_sx, j * av_sy,
+                                    n, mr, mx, my, av_sq[av_np + k] / dn - mx * mx, av_sq[2 * av_np + k] / dn - my * my,
+                                    av_xy[k] / dn - mx * my);
+                        }
+                        fprintf(fm, "\n");
+                    }
+                }
+                fclose(fm);
+                if ((rc = iblb_reset_average(ctx))) return die(ctx, rc, "iblb_reset_average");
+            }
+            av_first = false;
             if ((rc = iblb_get_flux(ctx, &Q))) return die(ctx, rc, "iblb_get_flux");
             if (lead) {
                 fsB.open(flux.c_str(), ofstream::app);

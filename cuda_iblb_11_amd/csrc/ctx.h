@@ -1,6 +1,7 @@
 // ctx.h — the context of the fused C ABI (include/iblb.h part 2) and the host helpers shared by
 // its translation units:
-//   iblb_ctx.hip   lifecycle, state, Lagrangian points, readers, point sampling and tracers, checkpoint / restart
+//   iblb_ctx.hip   lifecycle, state, Lagrangian points, readers, point sampling and tracers, averaged fields,
+//                  checkpoint / restart
 //   ctx_step.hip   halo exchange, the one-step / two-step / deep schedules, iblb_step, local and
 //                  RCCL groups, the output gather
 //   ctx_band.hip   the IB band cycle (K iterations per cycle with an owed force every iteration)
@@ -172,6 +173,19 @@ struct iblb_ctx {
     int tr_stride = 1;
     long long tr_next = 0;     // the iteration after which the next update runs
     long long tr_updates = 0;  // updates done since iblb_set_tracers
+    // time- and phase-averaged fields (iblb_set_average).  av_fields == 0: none, and iblb_step takes the
+    // path it took before there was averaging.  With averaging iblb_step stops at the iterations av_next,
+    // av_next + av_stride, ... and adds a sample to bin av_samples % av_nbins there (average_update).
+    // av_buf: [av_nbins][av_planes][av_win.nx * av_win.ny] doubles, a plane in the order the accumulate
+    // kernel's lanes run (y fastest); the planes of a bin: the sums of the set bits of av_fields in
+    // ascending order, their squares' sums (IBLB_AVG_SQ), then ux*uy (IBLB_AVG_UXUY)
+    double* av_buf = nullptr;
+    iblb_window av_win{};
+    unsigned av_fields = 0, av_flags = 0;
+    int av_stride = 1, av_nbins = 1, av_planes = 0;
+    long long av_next = 0;     // the iteration after which the next sample is taken
+    long long av_samples = 0;  // samples taken since iblb_set_average / iblb_reset_average
+    std::vector<long long> av_count;  // samples per bin
     // state machine
     int phase = iblbh::PH_EMPTY;
     long long t = 0;
@@ -354,6 +368,7 @@ int set_wait_ticks(iblb_ctx* c);  // wait_ticks from wait_timeout_s and the devi
 int hold_release(iblb_ctx* c);    // join the test hold's host thread (IBLB_TEST_HOLD)
 int prepare_read(iblb_ctx* c);
 int tracer_update(iblb_ctx* c);  // iblb_ctx.hip: one update of the tracers from the current state (no host synchronise)
+int average_update(iblb_ctx* c);  // iblb_ctx.hip: one sample of the averaged fields from the current state (no host synchronise)
 int free_boot(iblb_ctx* c);
 int alloc_zero(iblb_ctx* c, void** p, size_t bytes);
 int run_cilia(iblb_ctx* c);

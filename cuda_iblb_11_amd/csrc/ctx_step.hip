@@ -722,19 +722,27 @@ int iblb_step(iblb_ctx* c, int nsteps) {
     int rc = check_ready(c);
     if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    if (c->tr_n == 0) {
+    const bool tracers = c->tr_n > 0, average = c->av_fields != 0;
+    if (!tracers && !average) {
         if ((rc = step_call(c, nsteps))) return rc;
     } else {
-        // passive tracers: the call is cut at their update iterations; each piece (at most tr_stride
-        // iterations) is scheduled as a call of its own, then the tracers move with that state held
-        // fixed, as if the caller had stepped the piece, sampled u and updated them
+        // passive tracers and averaged fields: the call is cut at their event iterations (the union of the
+        // tracers' updates and the averages' samples); each piece (at most the smaller stride) is scheduled
+        // as a call of its own, then with that state held fixed the tracers move and the sample is added,
+        // as if the caller had stepped the piece, read the fields and done both on the host.  Neither
+        // changes the state: at a common iteration their order is free
         for (int done = 0; done < nsteps;) {
-            const long long to_update = c->tr_next - c->t;
-            if (to_update < 1) return fail(c, IBLB_ERR_STATE, "tracers: the next update iteration is not ahead of the state");
-            const int piece = (int)std::min<long long>(nsteps - done, to_update);
+            long long next = LLONG_MAX;
+            if (tracers) next = std::min(next, c->tr_next);
+            if (average) next = std::min(next, c->av_next);
+            const long long to_event = next - c->t;
+            if (to_event < 1)
+                return fail(c, IBLB_ERR_STATE, "tracers / averages: the next event iteration is not ahead of the state");
+            const int piece = (int)std::min<long long>(nsteps - done, to_event);
             if ((rc = step_call(c, piece))) return rc;
             done += piece;
-            if (c->t == c->tr_next && (rc = tracer_update(c))) return rc;
+            if (tracers && c->t == c->tr_next && (rc = tracer_update(c))) return rc;
+            if (average && c->t == c->av_next && (rc = average_update(c))) return rc;
         }
     }
     if ((rc = band_join(c))) return rc;

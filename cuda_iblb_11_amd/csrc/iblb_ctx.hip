@@ -1,5 +1,6 @@
 // iblb_ctx.hip — the fused context API of include/iblb.h: lifecycle, state, Lagrangian points,
-// readers in the reference layouts, point sampling and passive tracers, the output gather and checkpoint / restart.  Time stepping is
+// readers in the reference layouts, point sampling and passive tracers, averaged fields, the output gather and
+// checkpoint / restart.  Time stepping is
 // in ctx_step.hip, the IB band cycle in ctx_band.hip; the context itself in ctx.h.
 #include <cmath>
 #include <cstdio>
@@ -466,7 +467,7 @@ void iblb_destroy(iblb_ctx* c) {
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     void* bufs[] = {c->g_alloc, c->cil_samples, c->cil_lasts, c->cil_bpoints, c->rho0, c->u0, c->force0, c->d_s,
                     c->d_us, c->d_Fs, c->d_eps, c->d_Fs_sum, c->fd_alloc, c->fl_alloc, c->d_Q, c->red_buf, c->d_sch_s,
-                    c->d_sch_us, c->d_sch_eps, c->tr_x, c->tr_y, c->tr_laps};
+                    c->d_sch_us, c->d_sch_eps, c->tr_x, c->tr_y, c->tr_laps, c->av_buf};
     for (void* p : bufs)
         if (p) (void)hipFree(p);
     if (c->sig) (void)hipFree(c->sig);
@@ -541,6 +542,7 @@ int iblb_set_state(iblb_ctx* c, const double* rho, const double* u, const double
     c->ghost = 0;
     c->bnd_w = INT_MAX;
     if (c->tr_n > 0) c->tr_next = c->tr_stride;  // the tracers stay; their updates count from the new state
+    if (c->av_fields) c->av_next = c->av_stride;  // so do the averages: sums and counts kept, samples from the new state
     return IBLB_OK;
 }
 
@@ -1205,6 +1207,157 @@ int iblb_tracer_count(iblb_ctx* c, long long* n, int* stride, long long* updates
 
 }  // extern "C"
 
+// ---- time- and phase-averaged fields ----------------------------------------------------------------
+namespace iblbh {
+
+static void average_free(iblb_ctx* c) {
+    if (c->av_buf) (void)hipFree(c->av_buf);
+    c->av_buf = nullptr;
+    c->av_win = iblb_window{};
+    c->av_fields = c->av_flags = 0;
+    c->av_stride = c->av_nbins = 1;
+    c->av_planes = 0;
+    c->av_next = 0;
+    c->av_samples = 0;
+    c->av_count.clear();
+}
+
+static size_t average_bin_elems(const iblb_ctx* c) {
+    return (size_t)c->av_planes * (size_t)c->av_win.nx * (size_t)c->av_win.ny;
+}
+
+// One sample of the averaged fields from the current state, on the context's stream: the state prepared
+// as for a reader (the band streams joined, the owed IB force evaluated), then one launch.
+int average_update(iblb_ctx* c) {
+    if (!single_slab(c))  // the context joined a group after iblb_set_average: its window is the whole lattice's
+        return fail(c, IBLB_ERR_UNSUPPORTED, "averaging: a lone slab only; remove it before joining a group");
+    int rc = band_join(c);
+    if (rc || (rc = prepare_read(c))) return rc;
+    const int bin = (int)(c->av_samples % c->av_nbins);
+    const FieldsArgs a = window_args(c, c->av_win, 0, c->av_win.nx, c->av_fields);
+    double* acc = c->av_buf + (size_t)bin * average_bin_elems(c);
+    if (is_f64(c))
+        HIP_TRY(c, launch_average_accum<double>(gptr<double>(c, c->cur), c->L, halo_of<double>(c, c->cur), a, c->av_flags,
+                                                acc, c->stream));
+    else
+        HIP_TRY(c, launch_average_accum<float>(gptr<float>(c, c->cur), c->L, halo_of<float>(c, c->cur), a, c->av_flags, acc,
+                                               c->stream));
+    c->av_next += c->av_stride;
+    c->av_samples++;
+    c->av_count[bin]++;
+    return IBLB_OK;
+}
+
+}  // namespace iblbh
+
+extern "C" {
+
+int iblb_set_average(iblb_ctx* c, const iblb_window* w, unsigned fields, int stride, int nbins, unsigned flags) {
+    if (!c) return IBLB_ERR_ARG;
+    const unsigned known = IBLB_FIELD_RHO | IBLB_FIELD_UX | IBLB_FIELD_UY | IBLB_FIELD_VORT | IBLB_FIELD_SXX |
+                           IBLB_FIELD_SXY | IBLB_FIELD_SYY;
+    const bool remove = fields == 0 && !w;
+    if (!remove) {
+        if (fields == 0 || (fields & ~known)) return fail(c, IBLB_ERR_ARG, "fields: no field or an unknown IBLB_FIELD_* bit");
+        if (flags & ~(unsigned)(IBLB_AVG_SQ | IBLB_AVG_UXUY)) return fail(c, IBLB_ERR_ARG, "flags: an unknown IBLB_AVG_* bit");
+        if ((flags & IBLB_AVG_UXUY) && (fields & (IBLB_FIELD_UX | IBLB_FIELD_UY)) != (IBLB_FIELD_UX | IBLB_FIELD_UY))
+            return fail(c, IBLB_ERR_ARG, "IBLB_AVG_UXUY needs both IBLB_FIELD_UX and IBLB_FIELD_UY");
+        if (stride < 1) return fail(c, IBLB_ERR_ARG, "stride must be >= 1");
+        if (nbins < 1) return fail(c, IBLB_ERR_ARG, "nbins must be >= 1");
+    }
+    iblb_window win;
+    int lo = 0, nxl = 0;
+    int rc = window_part(c, w, &win, &lo, &nxl);
+    if (rc) return rc;
+    if (!single_slab(c))
+        return fail(c, IBLB_ERR_UNSUPPORTED,
+                    "iblb_set_average: a lone slab only (averaging on the slabs of a group is not built)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (remove) {
+        average_free(c);
+        return IBLB_OK;
+    }
+    // the new accumulators first: a failed allocation leaves the previous set as it was
+    const int nf = __builtin_popcount(fields);
+    const int planes = nf * ((flags & IBLB_AVG_SQ) ? 2 : 1) + ((flags & IBLB_AVG_UXUY) ? 1 : 0);
+    const long long cells = (long long)win.nx * win.ny;  // at most the lattice's
+    if (cells > LLONG_MAX / (long long)sizeof(double) / planes / nbins)
+        return fail(c, IBLB_ERR_NOMEM, "iblb_set_average: the accumulators exceed the address space");
+    const size_t bytes = (size_t)cells * planes * nbins * sizeof(double);
+    DevBuf d;
+    HIP_TRY(c, hipMalloc(&d.p, bytes));
+    HIP_TRY(c, hipMemsetAsync(d.p, 0, bytes, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    average_free(c);
+    c->av_buf = (double*)d.p;
+    d.p = nullptr;
+    c->av_win = win;
+    c->av_fields = fields;
+    c->av_flags = flags;
+    c->av_stride = stride;
+    c->av_nbins = nbins;
+    c->av_planes = planes;
+    c->av_next = c->t + stride;
+    c->av_samples = 0;
+    c->av_count.assign((size_t)nbins, 0);
+    return IBLB_OK;
+}
+
+int iblb_reset_average(iblb_ctx* c) {
+    if (!c) return IBLB_ERR_ARG;
+    if (!c->av_fields) return fail(c, IBLB_ERR_STATE, "iblb_reset_average: no averaging is set");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemsetAsync(c->av_buf, 0, (size_t)c->av_nbins * average_bin_elems(c) * sizeof(double), c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->av_next = c->t + c->av_stride;
+    c->av_samples = 0;
+    c->av_count.assign((size_t)c->av_nbins, 0);
+    return IBLB_OK;
+}
+
+int iblb_get_average(iblb_ctx* c, int bin, double* sum, double* sum_sq, double* sum_uxuy, long long* samples) {
+    if (!c) return IBLB_ERR_ARG;
+    if (!c->av_fields) return fail(c, IBLB_ERR_STATE, "iblb_get_average: no averaging is set");
+    if (bin < 0 || bin >= c->av_nbins) return fail(c, IBLB_ERR_ARG, "bin is outside [0, nbins)");
+    if (sum_sq && !(c->av_flags & IBLB_AVG_SQ)) return fail(c, IBLB_ERR_ARG, "sum_sq was not requested (IBLB_AVG_SQ)");
+    if (sum_uxuy && !(c->av_flags & IBLB_AVG_UXUY))
+        return fail(c, IBLB_ERR_ARG, "sum_uxuy was not requested (IBLB_AVG_UXUY)");
+    if (sum || sum_sq || sum_uxuy) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        // the whole bin transposed into the ABI's layout on the device, then whole planes copied
+        const size_t plane = (size_t)c->av_win.nx * c->av_win.ny, n = average_bin_elems(c);
+        const int nf = __builtin_popcount(c->av_fields);
+        DevBuf d;
+        HIP_TRY(c, hipMalloc(&d.p, n * sizeof(double)));
+        HIP_TRY(c, launch_average_readout(c->av_buf + (size_t)bin * n, c->av_win.nx, c->av_win.ny, c->av_planes,
+                                          (double*)d.p, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        const double* t = (const double*)d.p;
+        if (sum) HIP_TRY(c, hipMemcpy(sum, t, nf * plane * sizeof(double), hipMemcpyDeviceToHost));
+        if (sum_sq) HIP_TRY(c, hipMemcpy(sum_sq, t + nf * plane, nf * plane * sizeof(double), hipMemcpyDeviceToHost));
+        if (sum_uxuy)
+            HIP_TRY(c, hipMemcpy(sum_uxuy, t + (size_t)(c->av_planes - 1) * plane, plane * sizeof(double),
+                                 hipMemcpyDeviceToHost));
+    }
+    if (samples) *samples = c->av_count[(size_t)bin];
+    return IBLB_OK;
+}
+
+int iblb_average_info(iblb_ctx* c, iblb_window* w, unsigned* fields, int* stride, int* nbins, unsigned* flags,
+                      long long* samples_total) {
+    if (!c) return IBLB_ERR_ARG;
+    if (w) *w = c->av_win;
+    if (fields) *fields = c->av_fields;
+    if (stride) *stride = c->av_stride;
+    if (nbins) *nbins = c->av_nbins;
+    if (flags) *flags = c->av_flags;
+    if (samples_total) *samples_total = c->av_samples;
+    return IBLB_OK;
+}
+
+}  // extern "C"
+
 // ---- checkpoint / restart -------------------------------------------------------------------------
 // File: 8-byte magic, 12 int64 fields, 6 doubles, then the stored populations g (plane i, column
 // xc, rows y; storage precision, no padding), the Lagrangian points and the cilia buffers.
@@ -1320,6 +1473,7 @@ int iblb_load_checkpoint(iblb_ctx* c, const char* path) {
     c->ib_state = IB_NONE;
     c->phase = PH_EMPTY;
     tracers_free(c);  // a checkpoint holds no tracers (the caller saves them with iblb_get_tracers)
+    average_free(c);  // nor averages
     if (iv[CK_CILIA]) {
         iblb_cilia k{(int)iv[CK_CNUM], dv[CK_CSPACE], (int)iv[CK_CT], (int)iv[CK_CPSTEP]};
         if ((rc = iblb_set_cilia(c, &k))) return rc;

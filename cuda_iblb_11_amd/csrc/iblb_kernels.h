@@ -246,6 +246,18 @@ template <typename T>
 hipError_t launch_tracer_advect(const T* g, Layout L, Halo<T> H, const FieldsArgs& a, long n, int stride, double* x,
                                 double* y, int* laps, hipStream_t s);
 
+// Time- and phase-averaged fields (average_kernels.hip; include/iblb.h iblb_set_average).  One bin's
+// accumulators are `planes` planes of nxl * nyw doubles in the order the lanes run, [plane][il*nyw + j]:
+// the sums of the set bits of a.fields in ascending order, then their sums of squares (IBLB_AVG_SQ),
+// then one plane of ux*uy (IBLB_AVG_UXUY).
+// Adds the samples of FieldsArgs, each evaluated once by the device functions of field_eval.h, into the
+// bin at acc.  Vorticity as launch_fields_out: a lone slab only.
+template <typename T>
+hipError_t launch_average_accum(const T* g, Layout L, Halo<T> H, const FieldsArgs& a, unsigned flags, double* acc,
+                                hipStream_t s);
+// The planes of one bin transposed into iblb_get_fields' layout: out[(p*nyw + j)*nxl + il].
+hipError_t launch_average_readout(const double* acc, int nxl, int nyw, int planes, double* out, hipStream_t s);
+
 // q(u^t) of the current state for the flux column (added to *out).
 template <typename T>
 hipError_t launch_flux(const T* g, Layout L, Halo<T> H, const double* fdense, long fplane,

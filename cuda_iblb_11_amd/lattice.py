@@ -386,6 +386,65 @@ class Lattice:
         self._check(self._lib.iblb_get_tracers(self._h, _ptr(x), _ptr(y), _ptr(laps)))
         return x, y, laps
 
+    # -- time- and phase-averaged fields --------------------------------------------------------
+    def set_average(self, names, window=None, stride: int = 1, nbins: int = 1, squares: bool = False,
+                    uxuy: bool = False) -> None:
+        """Sums of the named fields over `window` that `step` accumulates on the device: one sample
+        every `stride` iterations, sample m into bin m % nbins (iblb_set_average).  squares: also the
+        sums of v*v; uxuy: also the sum of ux*uy (needs "ux" and "uy").  Empty names remove
+        averaging.  A lone slab only."""
+        names = [names] if isinstance(names, str) else list(names)
+        unknown = [n for n in names if n not in L.FIELDS]
+        if unknown:
+            raise ValueError(f"fields must be chosen from {sorted(L.FIELDS)}, got {names}")
+        if not names:
+            self._check(self._lib.iblb_set_average(self._h, None, 0, 1, 1, 0))
+            return
+        w = _window(window)
+        bits = sum(L.FIELDS[n] for n in set(names))
+        flags = (L.AVG_SQ if squares else 0) | (L.AVG_UXUY if uxuy else 0)
+        self._check(self._lib.iblb_set_average(self._h, None if w is None else C.byref(w), bits, int(stride),
+                                               int(nbins), flags))
+
+    def reset_average(self) -> None:
+        """Zero the sums and counts; the next sample is number 0, `stride` iterations from now
+        (iblb_reset_average)."""
+        self._check(self._lib.iblb_reset_average(self._h))
+
+    def average_info(self) -> dict:
+        """{"window": (x0, y0, nx, ny, sx, sy), "fields", "names", "stride", "nbins", "flags",
+        "samples_total"} of the averaging (iblb_average_info); fields == 0: none set."""
+        w, fields, stride, nbins = L.Window(), C.c_uint(0), C.c_int(0), C.c_int(0)
+        flags, total = C.c_uint(0), C.c_longlong(0)
+        self._check(self._lib.iblb_average_info(self._h, C.byref(w), C.byref(fields), C.byref(stride), C.byref(nbins),
+                                                C.byref(flags), C.byref(total)))
+        return {"window": (w.x0, w.y0, w.nx, w.ny, w.sx, w.sy), "fields": fields.value,
+                "names": [n for n, b in L.FIELDS.items() if fields.value & b], "stride": stride.value,
+                "nbins": nbins.value, "flags": flags.value, "samples_total": total.value}
+
+    def average(self, bin: int = 0) -> dict:
+        """The raw sums of one bin (iblb_get_average): {"samples": n, "sum": {name: (ny, nx)},
+        "sum_sq": {name: (ny, nx)} or None, "sum_uxuy": (ny, nx) array or None}, names in ascending
+        bit order."""
+        info = self.average_info()
+        if not info["fields"]:
+            self._check(self._lib.iblb_get_average(self._h, int(bin), None, None, None, None))
+        order = info["names"]
+        nx, ny = info["window"][2], info["window"][3]
+        s = np.empty((len(order), ny, nx))
+        sq = np.empty((len(order), ny, nx)) if info["flags"] & L.AVG_SQ else None
+        xy = np.empty((ny, nx)) if info["flags"] & L.AVG_UXUY else None
+        n = C.c_longlong(0)
+        self._check(self._lib.iblb_get_average(self._h, int(bin), _ptr(s), _ptr(sq), _ptr(xy), C.byref(n)))
+        return {"samples": n.value, "sum": {m: s[k] for k, m in enumerate(order)},
+                "sum_sq": None if sq is None else {m: sq[k] for k, m in enumerate(order)}, "sum_uxuy": xy}
+
+    def mean(self, bin: int = 0) -> dict:
+        """{name: sum / samples} of one bin (NaN where the bin holds no sample)."""
+        a = self.average(bin)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return {m: v / float(a["samples"]) for m, v in a["sum"].items()}
+
     @property
     def steps(self) -> int:
         n = C.c_longlong(0)

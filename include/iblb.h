@@ -353,6 +353,53 @@ int iblb_get_tracers(iblb_ctx* ctx, double* x, double* y, int* laps);   /* [n] e
 /* Tracers set, their stride and the updates done since iblb_set_tracers (any may be NULL). */
 int iblb_tracer_count(iblb_ctx* ctx, long long* n, int* stride, long long* updates);
 
+/* Time- and phase-averaged fields: sums of chosen fields over a window that the context itself accumulates
+ * on the device while iblb_step runs, so that a beat average (the mean flow, its fluctuation <u'u'>, the flow
+ * at a given phase of the beat) needs no readback per sample and keeps the deep sweep between samples.
+ * `w` and `fields` are those of iblb_get_fields (the seven IBLB_FIELD_* bits; NULL = the whole lattice at
+ * stride 1); stride >= 1, nbins >= 1; flags: */
+#define IBLB_AVG_SQ   1   /* also accumulate v*v of every requested field            */
+#define IBLB_AVG_UXUY 2   /* also accumulate ux*uy (needs IBLB_FIELD_UX and _UY)      */
+/* iblb_set_average validates its arguments, allocates zeroed accumulators on the device (per bin one plane of
+ * w.ny * w.nx doubles per requested field, as many again under IBLB_AVG_SQ, one more under IBLB_AVG_UXUY) and
+ * records t0 = iblb_get_step.  It replaces any previous set; fields == 0 with w == NULL removes averaging, and
+ * iblb_step is then exactly what it is without it.  A bad window, fields == 0 with a window, an unknown field
+ * bit or flag, IBLB_AVG_UXUY without both IBLB_FIELD_UX and IBLB_FIELD_UY, stride < 1 or nbins < 1:
+ * IBLB_ERR_ARG, checked before anything is touched.  A slab of a local or RCCL group: IBLB_ERR_UNSUPPORTED.
+ * Any error, IBLB_ERR_NOMEM included, leaves the previous set as it was.
+ * Sampling rule.  After the iterations t0 + stride, t0 + 2 stride, ... the context takes sample number
+ * m = 0, 1, 2, ... of the state of that iteration, and sample m goes to bin m % nbins: with stride * nbins equal
+ * to the beat period, bin b holds the average at phase b.  For every window sample (i, j) and the k-th set bit of
+ * `fields`, with v the value iblb_get_fields returns for that cell at that moment, bit for bit:
+ *   sum = sum + v;   sum_sq = sum_sq + v*v  (IBLB_AVG_SQ);   sum_uxuy = sum_uxuy + ux*uy  (IBLB_AVG_UXUY)
+ * in double, one rounding per operation, no contraction, in sample order; the bin's sample count goes up by
+ * one.  Nothing is filtered: a non-finite v makes that cell's sums non-finite.  No summation is compensated.
+ * iblb_step(nsteps) with averaging cuts the call at the sample iterations and schedules each piece (at most
+ * `stride` iterations) as a call of its own; the result is by definition that of the caller doing
+ * iblb_step(piece), then iblb_get_fields, then adding on the host.  Samples count on across calls.  With
+ * tracers set as well the call is cut at the union of both event sets; at a common iteration both run, and
+ * since neither changes the state their order is free.  A stride >= K (IBLB_SWEEP_DEPTH) keeps the deep sweep
+ * between samples; stride 1 costs the one-step path at every iteration.  One sample is one launch on the
+ * context's stream, one lane per window sample, without a host synchronise.
+ * iblb_reset_average zeroes the sums and counts and sets t0 to the current step (the next sample is number 0,
+ * `stride` iterations later); IBLB_ERR_STATE if no averaging is set.
+ * iblb_get_average returns the raw sums of one bin and its sample count; means and variances are the caller's
+ * division (mean = sum/samples, var = sum_sq/samples - mean^2), so that the result stays exactly checkable.
+ * sum and sum_sq are [nf * w.ny * w.nx] in iblb_get_fields' layout, out[(k*ny + j)*nx + i]; sum_uxuy is
+ * [w.ny * w.nx]; any of the pointers may be NULL.  A non-NULL pointer to a plane that was not requested
+ * (sum_sq without IBLB_AVG_SQ, sum_uxuy without IBLB_AVG_UXUY) or a bin outside [0, nbins): IBLB_ERR_ARG, nothing
+ * written.  No averaging set: IBLB_ERR_STATE.
+ * iblb_average_info returns the window (resolved: NULL became the whole lattice), fields, stride, nbins, flags
+ * and the samples taken since the set or the last reset (any pointer may be NULL); fields == 0: none set.
+ * iblb_set_state keeps the accumulators and counts and re-bases t0 to the new state's step count 0: the next
+ * sample follows `stride` iterations later.  Checkpoints do not hold averages: iblb_load_checkpoint removes
+ * averaging.  iblb_destroy frees the accumulators. */
+int iblb_set_average(iblb_ctx* ctx, const iblb_window* w, unsigned fields, int stride, int nbins, unsigned flags);
+int iblb_reset_average(iblb_ctx* ctx);
+int iblb_get_average(iblb_ctx* ctx, int bin, double* sum, double* sum_sq, double* sum_uxuy, long long* samples);
+int iblb_average_info(iblb_ctx* ctx, iblb_window* w, unsigned* fields, int* stride, int* nbins, unsigned* flags,
+                      long long* samples_total);
+
 /* Timing: when enabled (1) every collide-stream launch is bracketed by HIP events on the
  * stream it runs on; iblb_get_timing() returns the sums (and resets them if reset).  enabled = 2:
  * only the deep (K-iteration) launches are timed, by their own dispatch / completion signals (no
