@@ -536,6 +536,24 @@ int iblb_set_state(iblb_ctx* c, const double* rho, const double* u, const double
         if ((rc = reset_cilia_state(c))) return rc;
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
+    if (c->sch_n > 0) {  // a schedule stays and restarts with the state: iteration i uses entry i
+        // the entry in use becomes the static points, as in retire_points (readers before the first
+        // step see them); no owed force (the old state is gone) and nothing collective
+        if (c->sch_cur >= 0 && c->ns > 0) {
+            const size_t ns = (size_t)c->ns;
+            HIP_TRY(c, hipMemcpyAsync(c->d_s, pts_s(c), 2 * ns * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(c->d_us, pts_us(c), 2 * ns * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(c->d_eps, pts_eps(c), ns * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            const size_t e = (size_t)c->sch_cur;
+            c->pts_host.assign(c->sch_x.begin() + e * 2 * ns, c->sch_x.begin() + (e + 1) * 2 * ns);
+        }
+        c->sch_cur = -1;
+        c->sch_t0 = 0;
+        c->sch_x_prev.clear();
+        c->band_valid = false;
+        c->band_retry_t = 0;
+    }
     c->phase = PH_BOOT;
     c->t = 0;
     c->ib_state = IB_NONE;

@@ -202,7 +202,10 @@ int iblb_set_lagrangian(iblb_ctx* ctx, int ns, const float* s, const float* u_s,
  * those of entry nsteps-1.  Same result as iblb_set_lagrangian(entry i) before each of those
  * iterations, but iblb_step can then advance several iterations per launch (IB band cycle)
  * where the points of one cycle force only part of the lattice.  s, u_s [nsteps][2ns] xy,
- * epsilon [nsteps][ns] (NULL = all 1).  iblb_set_lagrangian / iblb_set_cilia end the schedule. */
+ * epsilon [nsteps][ns] (NULL = all 1).  iblb_set_lagrangian / iblb_set_cilia end the schedule.
+ * iblb_set_state keeps a schedule and re-bases it: iteration i of the new state uses entry i
+ * (clamped to the last).  Until the first step iblb_get_lagrangian returns the points that were
+ * current before the call. */
 int iblb_set_lagrangian_steps(iblb_ctx* ctx, int nsteps, int ns, const float* s, const float* u_s,
                               const int* epsilon);
 
