@@ -1,10 +1,13 @@
 // ctx.h — the context of the fused C ABI (include/iblb.h part 2) and the host helpers shared by
 // its translation units:
-//   iblb_ctx.hip   lifecycle, state, Lagrangian points, readers, point sampling and tracers, averaged fields,
-//                  checkpoint / restart
+//   iblb_ctx.hip   lifecycle, state, Lagrangian points, timing, checkpoint / restart
+//   ctx_read.hip   the readers: the current state to the host in the reference layouts, windowed
+//                  fields and reductions, point sampling, the output gather
+//   ctx_observe.hip  what iblb_step runs between the pieces of a call: passive tracers, averaged fields
 //   ctx_step.hip   halo exchange, the one-step / two-step / deep schedules, iblb_step, local and
-//                  RCCL groups, the output gather
+//                  RCCL groups
 //   ctx_band.hip   the IB band cycle (K iterations per cycle with an owed force every iteration)
+// Every reader and observer is built from the read scaffold below (with_state ... read_back).
 //   band_plan.h    the band cycle's planner: pure host functions (no HIP), checked on the CPU
 //
 // Time-step bookkeeping.  The reference iteration (main.cu:852-909) is
@@ -35,6 +38,7 @@
 #include <array>
 #include <climits>
 #include <cstdint>
+#include <initializer_list>
 #include <string>
 #include <thread>
 #include <vector>
@@ -58,6 +62,24 @@ constexpr int BAND_PIN_SLOTS = 4;
 
 long env_long(const char* name, long dflt);
 extern std::string g_create_error;
+
+// Scratch device buffer freed at scope exit.
+struct DevBuf {
+    void* p = nullptr;
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
+};
+
+// An observer's schedule: iblb_step stops at the iterations next, next + stride, ... and runs it there.
+struct Periodic {
+    int stride = 1;
+    long long next = 0;   // the iteration after which it runs next
+    long long count = 0;  // runs since it was set (the averages: or reset)
+    void arm(long long t) { next = t + stride; }  // the first run `stride` iterations after t; count stays
+    void advance() { next += stride; ++count; }
+    void clear() { *this = Periodic{}; }
+};
 
 }  // namespace iblbh
 
@@ -164,27 +186,22 @@ struct iblb_ctx {
     size_t red_cap = 0;  // doubles allocated
     std::vector<double> red_host;
     // passive tracers (iblb_set_tracers): SoA positions in double, wraps in x counted in laps.  tr_n == 0:
-    // none, and iblb_step takes the path it took before there were tracers.  With tracers iblb_step
-    // stops at the iterations tr_next, tr_next + tr_stride, ... and updates them there (tracer_update)
+    // none.  With tracers iblb_step stops at the iterations of tr_ev and updates them there (ctx_observe.hip)
     double* tr_x = nullptr;
     double* tr_y = nullptr;
     int* tr_laps = nullptr;
     long long tr_n = 0;
-    int tr_stride = 1;
-    long long tr_next = 0;     // the iteration after which the next update runs
-    long long tr_updates = 0;  // updates done since iblb_set_tracers
-    // time- and phase-averaged fields (iblb_set_average).  av_fields == 0: none, and iblb_step takes the
-    // path it took before there was averaging.  With averaging iblb_step stops at the iterations av_next,
-    // av_next + av_stride, ... and adds a sample to bin av_samples % av_nbins there (average_update).
+    iblbh::Periodic tr_ev;  // count: updates done since iblb_set_tracers
+    // time- and phase-averaged fields (iblb_set_average).  av_fields == 0: none.  With averaging iblb_step
+    // stops at the iterations of av_ev and adds a sample to bin av_ev.count % av_nbins there.
     // av_buf: [av_nbins][av_planes][av_win.nx * av_win.ny] doubles, a plane in the order the accumulate
     // kernel's lanes run (y fastest); the planes of a bin: the sums of the set bits of av_fields in
     // ascending order, their squares' sums (IBLB_AVG_SQ), then ux*uy (IBLB_AVG_UXUY)
     double* av_buf = nullptr;
     iblb_window av_win{};
     unsigned av_fields = 0, av_flags = 0;
-    int av_stride = 1, av_nbins = 1, av_planes = 0;
-    long long av_next = 0;     // the iteration after which the next sample is taken
-    long long av_samples = 0;  // samples taken since iblb_set_average / iblb_reset_average
+    int av_nbins = 1, av_planes = 0;
+    iblbh::Periodic av_ev;  // count: samples taken since iblb_set_average / iblb_reset_average
     std::vector<long long> av_count;  // samples per bin
     // state machine
     int phase = iblbh::PH_EMPTY;
@@ -367,8 +384,6 @@ int check_wait_err(iblb_ctx* c);  // after a synchronize: did an edge wave's wai
 int set_wait_ticks(iblb_ctx* c);  // wait_ticks from wait_timeout_s and the device's wall-clock rate
 int hold_release(iblb_ctx* c);    // join the test hold's host thread (IBLB_TEST_HOLD)
 int prepare_read(iblb_ctx* c);
-int tracer_update(iblb_ctx* c);  // iblb_ctx.hip: one update of the tracers from the current state (no host synchronise)
-int average_update(iblb_ctx* c);  // iblb_ctx.hip: one sample of the averaged fields from the current state (no host synchronise)
 int free_boot(iblb_ctx* c);
 int alloc_zero(iblb_ctx* c, void** p, size_t bytes);
 int run_cilia(iblb_ctx* c);
@@ -386,5 +401,76 @@ int cilia_schedule(iblb_ctx* c, int n);  // cilia kinematics of the next n itera
 int cilia_schedule_end(iblb_ctx* c);
 bool band_possible(const iblb_ctx* c);  // the band cycle may run on this context (points aside)
 int band_release(iblb_ctx* c);  // streams, events, pinned tables, scratch buffers
+
+// ---- readers (ctx_read.hip) ----
+// the window (NULL: the whole lattice) checked, and this slab's samples [*i_first, *i_first + *nxl) of it
+int window_part(iblb_ctx* c, const iblb_window* w, iblb_window* win, int* i_first, int* nxl);
+// the windowed kernels' arguments for samples [lo, lo + nxl) of win; point_args: their state-dependent part (no window)
+FieldsArgs window_args(iblb_ctx* c, const iblb_window& win, int lo, int nxl, unsigned fields);
+inline FieldsArgs point_args(iblb_ctx* c, unsigned fields) { return window_args(c, {0, 0, 1, 1, 1, 1}, 0, 1, fields); }
+int check_positions(iblb_ctx* c, long long n, const double* x, const double* y);
+int group_refused(iblb_ctx* c, const char* what);
+
+// ---- observers (ctx_observe.hip): run by iblb_step on the context's stream, no host synchronise ----
+long long next_event(const iblb_ctx* c);  // the next iteration at which an observer runs (LLONG_MAX: none set)
+int run_events(iblb_ctx* c);              // every observer due at c->t: the tracers, then the averages
+void tracers_free(iblb_ctx* c);
+void average_free(iblb_ctx* c);
+
+// ---- the read scaffold: what every reader and observer is made of ----
+// f(g, H): the populations and the halo of the current state, typed by the context's precision; the
+// launchers deduce their T from them.  Returns f's hipError_t.
+template <typename F>
+inline hipError_t with_state(iblb_ctx* c, F&& f) {
+    if (is_f64(c)) return f(gptr<double>(c, c->cur), halo_of<double>(c, c->cur));
+    return f(gptr<float>(c, c->cur), halo_of<float>(c, c->cur));
+}
+
+// the dense IB force of the current state (null: none evaluated, the body force alone)
+inline const double* ib_force(const iblb_ctx* c) { return c->ib_state == IB_READY ? c->fdense : nullptr; }
+
+constexpr unsigned IBLB_FIELD_ALL = IBLB_FIELD_RHO | IBLB_FIELD_UX | IBLB_FIELD_UY | IBLB_FIELD_VORT | IBLB_FIELD_SXX |
+                                    IBLB_FIELD_SXY | IBLB_FIELD_SYY;
+constexpr unsigned IBLB_QTY_ALL = IBLB_QTY_MOMX | IBLB_QTY_MOMY | IBLB_QTY_KE | IBLB_QTY_USQ;
+
+// at least one bit and none outside `known`: IBLB_FIELD_ALL, or with IBLB_QTY_ALL what iblb_reduce_fields takes
+inline int check_fields(iblb_ctx* c, unsigned fields, unsigned known = IBLB_FIELD_ALL) {
+    if (fields != 0 && !(fields & ~known)) return IBLB_OK;
+    return fail(c, IBLB_ERR_ARG, known & IBLB_QTY_ALL ? "fields: no quantity or an unknown IBLB_FIELD_* / IBLB_QTY_* bit"
+                                                      : "fields: no field or an unknown IBLB_FIELD_* bit");
+}
+
+inline int check_vorticity(iblb_ctx* c, unsigned fields) {
+    if (!(fields & IBLB_FIELD_VORT) || single_slab(c)) return IBLB_OK;
+    return fail(c, IBLB_ERR_UNSUPPORTED,
+                "vorticity needs the neighbour slabs' velocity and force: a lone slab only (compute it from "
+                "the gathered u)");
+}
+
+// n values summed over the slabs of an RCCL group, on the context's stream; a lone slab: nothing
+inline int group_sum(iblb_ctx* c, const void* send, void* recv, size_t n, ncclDataType_t type) {
+    if (!rccl_multi(c)) return IBLB_OK;
+    int rc = rccl_order(c, c->stream);
+    if (rc) return rc;
+    NCCL_TRY(c, ncclAllReduce(send, recv, n, type, ncclSum, c->comm, c->stream));
+    return IBLB_OK;
+}
+
+// The end of a read: the context's stream synchronised, then blocking copies to the host.  Null
+// destinations and empty copies are skipped (the synchronise is not).
+struct HostCopy {
+    void* host;
+    const void* dev;
+    size_t bytes;
+};
+inline int read_back(iblb_ctx* c, std::initializer_list<HostCopy> copies) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (const HostCopy& k : copies)
+        if (k.host && k.bytes) HIP_TRY(c, hipMemcpy(k.host, k.dev, k.bytes, hipMemcpyDeviceToHost));
+    return IBLB_OK;
+}
+inline int read_back(iblb_ctx* c, void* host, const void* dev, size_t bytes) {
+    return read_back(c, {{host, dev, bytes}});
+}
 
 }  // namespace iblbh

@@ -1,0 +1,239 @@
+// ctx_observe.hip — the observers of a context (ctx.h): what iblb_step runs between the pieces of a call
+// with the state held fixed.  Passive tracers (iblb_set_tracers) and time- and phase-averaged fields
+// (iblb_set_average), each on a Periodic schedule; iblb_step asks next_event where to cut a call and
+// run_events to run what is due there.  Built from the read scaffold of ctx.h like the readers.
+#include "ctx.h"
+
+namespace iblbh {
+
+void tracers_free(iblb_ctx* c) {
+    for (void* p : {(void*)c->tr_x, (void*)c->tr_y, (void*)c->tr_laps})
+        if (p) (void)hipFree(p);
+    c->tr_x = c->tr_y = nullptr;
+    c->tr_laps = nullptr;
+    c->tr_n = 0;
+    c->tr_ev.clear();
+}
+
+void average_free(iblb_ctx* c) {
+    if (c->av_buf) (void)hipFree(c->av_buf);
+    c->av_buf = nullptr;
+    c->av_win = iblb_window{};
+    c->av_fields = c->av_flags = 0;
+    c->av_nbins = 1;
+    c->av_planes = 0;
+    c->av_ev.clear();
+    c->av_count.clear();
+}
+
+static size_t average_bin_elems(const iblb_ctx* c) {
+    return (size_t)c->av_planes * (size_t)c->av_win.nx * (size_t)c->av_win.ny;
+}
+
+// One update of the tracers from the current state, on the context's stream: the state prepared as
+// for a reader (the band streams joined, the owed IB force evaluated), then one launch.
+static int tracer_update(iblb_ctx* c) {
+    int rc = band_join(c);
+    if (rc || (rc = prepare_read(c))) return rc;
+    const FieldsArgs a = point_args(c, IBLB_FIELD_UX | IBLB_FIELD_UY);
+    HIP_TRY(c, with_state(c, [&](auto* g, auto H) {
+        return launch_tracer_advect(g, c->L, H, a, (long)c->tr_n, c->tr_ev.stride, c->tr_x, c->tr_y, c->tr_laps, c->stream);
+    }));
+    c->tr_ev.advance();
+    return IBLB_OK;
+}
+
+// One sample of the averaged fields from the current state, on the context's stream: the state prepared
+// as for a reader (the band streams joined, the owed IB force evaluated), then one launch.
+static int average_update(iblb_ctx* c) {
+    if (!single_slab(c))  // the context joined a group after iblb_set_average: its window is the whole lattice's
+        return fail(c, IBLB_ERR_UNSUPPORTED, "averaging: a lone slab only; remove it before joining a group");
+    int rc = band_join(c);
+    if (rc || (rc = prepare_read(c))) return rc;
+    const int bin = (int)(c->av_ev.count % c->av_nbins);
+    const FieldsArgs a = window_args(c, c->av_win, 0, c->av_win.nx, c->av_fields);
+    double* acc = c->av_buf + (size_t)bin * average_bin_elems(c);
+    HIP_TRY(c, with_state(c, [&](auto* g, auto H) {
+        return launch_average_accum(g, c->L, H, a, c->av_flags, acc, c->stream);
+    }));
+    c->av_ev.advance();
+    c->av_count[bin]++;
+    return IBLB_OK;
+}
+
+long long next_event(const iblb_ctx* c) {
+    long long next = LLONG_MAX;
+    if (c->tr_n > 0) next = std::min(next, c->tr_ev.next);
+    if (c->av_fields) next = std::min(next, c->av_ev.next);
+    return next;
+}
+
+// Neither observer changes the state: at a common iteration their order is free
+int run_events(iblb_ctx* c) {
+    int rc = IBLB_OK;
+    if (c->tr_n > 0 && c->t == c->tr_ev.next && (rc = tracer_update(c))) return rc;
+    if (c->av_fields && c->t == c->av_ev.next) rc = average_update(c);
+    return rc;
+}
+
+}  // namespace iblbh
+
+using namespace iblbh;
+
+extern "C" {
+
+// ---- passive tracers ----------------------------------------------------------------------------------
+int iblb_set_tracers(iblb_ctx* c, long long n, const double* x, const double* y, int stride) {
+    if (!c) return IBLB_ERR_ARG;
+    if (n < 0) return fail(c, IBLB_ERR_ARG, "n is negative");
+    if (stride < 1) return fail(c, IBLB_ERR_ARG, "stride must be >= 1");
+    if (n > 0 && (!x || !y)) return fail(c, IBLB_ERR_ARG, "x or y is NULL");
+    if (!single_slab(c)) return group_refused(c, "iblb_set_tracers");
+    int rc = check_positions(c, n, x, y);
+    if (rc) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (n == 0) {
+        tracers_free(c);
+        return IBLB_OK;
+    }
+    // the new arrays first: a failed allocation leaves the previous tracers as they were
+    const size_t np = (size_t)n;
+    DevBuf dx, dy, dl;
+    HIP_TRY(c, hipMalloc(&dx.p, np * sizeof(double)));
+    HIP_TRY(c, hipMalloc(&dy.p, np * sizeof(double)));
+    HIP_TRY(c, hipMalloc(&dl.p, np * sizeof(int)));
+    HIP_TRY(c, hipMemcpy(dx.p, x, np * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(dy.p, y, np * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemsetAsync(dl.p, 0, np * sizeof(int), c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    tracers_free(c);
+    c->tr_x = (double*)dx.p;
+    c->tr_y = (double*)dy.p;
+    c->tr_laps = (int*)dl.p;
+    dx.p = dy.p = dl.p = nullptr;
+    c->tr_n = n;
+    c->tr_ev.stride = stride;
+    c->tr_ev.arm(c->t);
+    return IBLB_OK;
+}
+
+int iblb_get_tracers(iblb_ctx* c, double* x, double* y, int* laps) {
+    if (!c) return IBLB_ERR_ARG;
+    if (c->tr_n == 0) return IBLB_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t np = (size_t)c->tr_n;
+    return read_back(c, {{x, c->tr_x, np * sizeof(double)},
+                         {y, c->tr_y, np * sizeof(double)},
+                         {laps, c->tr_laps, np * sizeof(int)}});
+}
+
+int iblb_tracer_count(iblb_ctx* c, long long* n, int* stride, long long* updates) {
+    if (!c) return IBLB_ERR_ARG;
+    if (n) *n = c->tr_n;
+    if (stride) *stride = c->tr_ev.stride;
+    if (updates) *updates = c->tr_ev.count;
+    return IBLB_OK;
+}
+
+// ---- time- and phase-averaged fields ----------------------------------------------------------------
+int iblb_set_average(iblb_ctx* c, const iblb_window* w, unsigned fields, int stride, int nbins, unsigned flags) {
+    if (!c) return IBLB_ERR_ARG;
+    const bool remove = fields == 0 && !w;
+    int rc;
+    if (!remove) {
+        if ((rc = check_fields(c, fields))) return rc;
+        if (flags & ~(unsigned)(IBLB_AVG_SQ | IBLB_AVG_UXUY)) return fail(c, IBLB_ERR_ARG, "flags: an unknown IBLB_AVG_* bit");
+        if ((flags & IBLB_AVG_UXUY) && (fields & (IBLB_FIELD_UX | IBLB_FIELD_UY)) != (IBLB_FIELD_UX | IBLB_FIELD_UY))
+            return fail(c, IBLB_ERR_ARG, "IBLB_AVG_UXUY needs both IBLB_FIELD_UX and IBLB_FIELD_UY");
+        if (stride < 1) return fail(c, IBLB_ERR_ARG, "stride must be >= 1");
+        if (nbins < 1) return fail(c, IBLB_ERR_ARG, "nbins must be >= 1");
+    }
+    iblb_window win;
+    int lo = 0, nxl = 0;
+    if ((rc = window_part(c, w, &win, &lo, &nxl))) return rc;
+    if (!single_slab(c))
+        return fail(c, IBLB_ERR_UNSUPPORTED,
+                    "iblb_set_average: a lone slab only (averaging on the slabs of a group is not built)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (remove) {
+        average_free(c);
+        return IBLB_OK;
+    }
+    // the new accumulators first: a failed allocation leaves the previous set as it was
+    const int nf = __builtin_popcount(fields);
+    const int planes = nf * ((flags & IBLB_AVG_SQ) ? 2 : 1) + ((flags & IBLB_AVG_UXUY) ? 1 : 0);
+    const long long cells = (long long)win.nx * win.ny;  // at most the lattice's
+    if (cells > LLONG_MAX / (long long)sizeof(double) / planes / nbins)
+        return fail(c, IBLB_ERR_NOMEM, "iblb_set_average: the accumulators exceed the address space");
+    const size_t bytes = (size_t)cells * planes * nbins * sizeof(double);
+    DevBuf d;
+    HIP_TRY(c, hipMalloc(&d.p, bytes));
+    HIP_TRY(c, hipMemsetAsync(d.p, 0, bytes, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    average_free(c);
+    c->av_buf = (double*)d.p;
+    d.p = nullptr;
+    c->av_win = win;
+    c->av_fields = fields;
+    c->av_flags = flags;
+    c->av_nbins = nbins;
+    c->av_planes = planes;
+    c->av_ev.stride = stride;
+    c->av_ev.arm(c->t);
+    c->av_count.assign((size_t)nbins, 0);
+    return IBLB_OK;
+}
+
+int iblb_reset_average(iblb_ctx* c) {
+    if (!c) return IBLB_ERR_ARG;
+    if (!c->av_fields) return fail(c, IBLB_ERR_STATE, "iblb_reset_average: no averaging is set");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemsetAsync(c->av_buf, 0, (size_t)c->av_nbins * average_bin_elems(c) * sizeof(double), c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->av_ev.count = 0;
+    c->av_ev.arm(c->t);
+    c->av_count.assign((size_t)c->av_nbins, 0);
+    return IBLB_OK;
+}
+
+int iblb_get_average(iblb_ctx* c, int bin, double* sum, double* sum_sq, double* sum_uxuy, long long* samples) {
+    if (!c) return IBLB_ERR_ARG;
+    if (!c->av_fields) return fail(c, IBLB_ERR_STATE, "iblb_get_average: no averaging is set");
+    if (bin < 0 || bin >= c->av_nbins) return fail(c, IBLB_ERR_ARG, "bin is outside [0, nbins)");
+    if (sum_sq && !(c->av_flags & IBLB_AVG_SQ)) return fail(c, IBLB_ERR_ARG, "sum_sq was not requested (IBLB_AVG_SQ)");
+    if (sum_uxuy && !(c->av_flags & IBLB_AVG_UXUY))
+        return fail(c, IBLB_ERR_ARG, "sum_uxuy was not requested (IBLB_AVG_UXUY)");
+    if (sum || sum_sq || sum_uxuy) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        // the whole bin transposed into the ABI's layout on the device, then whole planes copied
+        const size_t plane = (size_t)c->av_win.nx * c->av_win.ny, n = average_bin_elems(c);
+        const size_t nf = (size_t)__builtin_popcount(c->av_fields);
+        DevBuf d;
+        HIP_TRY(c, hipMalloc(&d.p, n * sizeof(double)));
+        HIP_TRY(c, launch_average_readout(c->av_buf + (size_t)bin * n, c->av_win.nx, c->av_win.ny, c->av_planes,
+                                          (double*)d.p, c->stream));
+        const double* t = (const double*)d.p;
+        int rc = read_back(c, {{sum, t, nf * plane * sizeof(double)},
+                               {sum_sq, t + nf * plane, nf * plane * sizeof(double)},
+                               {sum_uxuy, t + (size_t)(c->av_planes - 1) * plane, plane * sizeof(double)}});
+        if (rc) return rc;
+    }
+    if (samples) *samples = c->av_count[(size_t)bin];
+    return IBLB_OK;
+}
+
+int iblb_average_info(iblb_ctx* c, iblb_window* w, unsigned* fields, int* stride, int* nbins, unsigned* flags,
+                      long long* samples_total) {
+    if (!c) return IBLB_ERR_ARG;
+    if (w) *w = c->av_win;
+    if (fields) *fields = c->av_fields;
+    if (stride) *stride = c->av_ev.stride;
+    if (nbins) *nbins = c->av_nbins;
+    if (flags) *flags = c->av_flags;
+    if (samples_total) *samples_total = c->av_ev.count;
+    return IBLB_OK;
+}
+
+}  // extern "C"

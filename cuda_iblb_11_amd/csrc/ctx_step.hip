@@ -1,6 +1,6 @@
 // ctx_step.hip — time stepping of a context (ctx.h): the ghost-column halo exchange, the one-step,
-// two-step and deep (K-iteration) schedules of a lone slab and of a slab of a group, iblb_step,
-// local groups, RCCL groups and the output gather.
+// two-step and deep (K-iteration) schedules of a lone slab and of a slab of a group, iblb_step
+// (cut at the observers' events, ctx_observe.hip), local groups and RCCL groups.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -128,14 +128,10 @@ int ensure_force(iblb_ctx* c) {
     size_t ev = 0;
     if ((rc = ev_begin(c, &ev))) return rc;
     if (single_slab(c)) {
-        if (is_f64(c))
-            HIP_TRY(c, launch_ib_point<double>(gptr<double>(c, c->cur), c->L, halo_of<double>(c, c->cur), c->nx, c->ns,
-                                               pts_s(c), pts_us(c), pts_eps(c), c->d_Fs, c->fdense, c->fplane, c->flags,
-                                               c->nch, 64 * c->V, c->stream));
-        else
-            HIP_TRY(c, launch_ib_point<float>(gptr<float>(c, c->cur), c->L, halo_of<float>(c, c->cur), c->nx, c->ns,
-                                              pts_s(c), pts_us(c), pts_eps(c), c->d_Fs, c->fdense, c->fplane, c->flags,
-                                              c->nch, 64 * c->V, c->stream));
+        HIP_TRY(c, with_state(c, [&](auto* g, auto H) {
+            return launch_ib_point(g, c->L, H, c->nx, c->ns, pts_s(c), pts_us(c), pts_eps(c), c->d_Fs, c->fdense,
+                                   c->fplane, c->flags, c->nch, 64 * c->V, c->stream);
+        }));
     } else {
         if (c->ncol < 3) return fail(c, IBLB_ERR_ARG, "immersed boundary across slabs needs >= 3 columns per slab");
         if ((rc = ib_ghost(c, c->g[c->cur], c->ghost, 0, c->ncol, pts_s(c), pts_us(c), pts_eps(c), 0, c->stream)))
@@ -722,28 +718,18 @@ int iblb_step(iblb_ctx* c, int nsteps) {
     int rc = check_ready(c);
     if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    const bool tracers = c->tr_n > 0, average = c->av_fields != 0;
-    if (!tracers && !average) {
-        if ((rc = step_call(c, nsteps))) return rc;
-    } else {
-        // passive tracers and averaged fields: the call is cut at their event iterations (the union of the
-        // tracers' updates and the averages' samples); each piece (at most the smaller stride) is scheduled
-        // as a call of its own, then with that state held fixed the tracers move and the sample is added,
-        // as if the caller had stepped the piece, read the fields and done both on the host.  Neither
-        // changes the state: at a common iteration their order is free
-        for (int done = 0; done < nsteps;) {
-            long long next = LLONG_MAX;
-            if (tracers) next = std::min(next, c->tr_next);
-            if (average) next = std::min(next, c->av_next);
-            const long long to_event = next - c->t;
-            if (to_event < 1)
-                return fail(c, IBLB_ERR_STATE, "tracers / averages: the next event iteration is not ahead of the state");
-            const int piece = (int)std::min<long long>(nsteps - done, to_event);
-            if ((rc = step_call(c, piece))) return rc;
-            done += piece;
-            if (tracers && c->t == c->tr_next && (rc = tracer_update(c))) return rc;
-            if (average && c->t == c->av_next && (rc = average_update(c))) return rc;
-        }
+    // The observers (ctx_observe.hip: passive tracers, averaged fields) cut the call at their event
+    // iterations: each piece (at most the smaller stride) is scheduled as a call of its own, then with that
+    // state held fixed the observers due there run, as if the caller had stepped the piece, read the fields
+    // and done their work on the host.  No observer: no event ahead, and the one piece is the whole call
+    for (int done = 0; done < nsteps;) {
+        const long long next = next_event(c);
+        const long long to_event = next == LLONG_MAX ? LLONG_MAX : next - c->t;
+        if (to_event < 1)
+            return fail(c, IBLB_ERR_STATE, "tracers / averages: the next event iteration is not ahead of the state");
+        const int piece = (int)std::min<long long>(nsteps - done, to_event);
+        if ((rc = step_call(c, piece)) || (rc = run_events(c))) return rc;
+        done += piece;
     }
     if ((rc = band_join(c))) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));

@@ -1,7 +1,7 @@
-// iblb_ctx.hip — the fused context API of include/iblb.h: lifecycle, state, Lagrangian points,
-// readers in the reference layouts, point sampling and passive tracers, averaged fields, the output gather and
-// checkpoint / restart.  Time stepping is
-// in ctx_step.hip, the IB band cycle in ctx_band.hip; the context itself in ctx.h.
+// iblb_ctx.hip — the fused context API of include/iblb.h: lifecycle, state, Lagrangian points, timing
+// and checkpoint / restart.  The readers are in ctx_read.hip, the tracers and averaged fields in
+// ctx_observe.hip, time stepping in ctx_step.hip, the IB band cycle in ctx_band.hip; the context itself
+// and the helpers they share in ctx.h.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -118,33 +118,7 @@ int free_boot(iblb_ctx* c) {
     return IBLB_OK;
 }
 
-// Scratch device buffer freed at scope exit.
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-};
-
 static size_t round_up(size_t v, size_t m) { return (v + m - 1) / m * m; }
-
-// rho [N] and u [2N] of the slab in the reference layout (j = y*ncol + xc), into device buffers,
-// on the context's stream.  The state must be prepared (prepare_read).
-static int macro_device(iblb_ctx* c, double* dr, double* du) {
-    if (c->phase == PH_BOOT) {
-        HIP_TRY(c, launch_field_out(c->rho0, dr, c->L, 1, c->fplane, 0., 0., c->stream));
-        HIP_TRY(c, launch_field_out(c->u0, du, c->L, 2, c->fplane, 0., 0., c->stream));
-        return IBLB_OK;
-    }
-    const double* fd = c->ib_state == IB_READY ? c->fdense : nullptr;
-    if (is_f64(c))
-        HIP_TRY(c, launch_macro_out<double>(gptr<double>(c, c->cur), c->L, halo_of<double>(c, c->cur), fd, c->fplane,
-                                            c->coef.gx, c->coef.gy, dr, du, c->stream));
-    else
-        HIP_TRY(c, launch_macro_out<float>(gptr<float>(c, c->cur), c->L, halo_of<float>(c, c->cur), fd, c->fplane,
-                                           c->coef.gx, c->coef.gy, dr, du, c->stream));
-    return IBLB_OK;
-}
 
 static std::vector<float> host_points(const float* s, size_t ns) { return std::vector<float>(s, s + 2 * ns); }
 
@@ -521,8 +495,7 @@ int iblb_set_state(iblb_ctx* c, const double* rho, const double* u, const double
         if (rc) return fail(c, rc, "initial equilibrium launch failed");
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
-    if (is_f64(c)) HIP_TRY(c, launch_pop_in<double>((const double*)d_f.p, gptr<double>(c, c->cur), c->L, c->stream));
-    else HIP_TRY(c, launch_pop_in<float>((const double*)d_f.p, gptr<float>(c, c->cur), c->L, c->stream));
+    HIP_TRY(c, with_state(c, [&](auto* g, auto) { return launch_pop_in((const double*)d_f.p, g, c->L, c->stream); }));
     HIP_TRY(c, launch_field_in((const double*)d_rho.p, c->rho0, c->L, 1, c->fplane, c->stream));
     HIP_TRY(c, launch_field_in((const double*)d_u.p, c->u0, c->L, 2, c->fplane, c->stream));
     HIP_TRY(c, launch_field_in((const double*)d_force.p, c->force0, c->L, 2, c->fplane, c->stream));
@@ -559,8 +532,8 @@ int iblb_set_state(iblb_ctx* c, const double* rho, const double* u, const double
     c->ib_state = IB_NONE;
     c->ghost = 0;
     c->bnd_w = INT_MAX;
-    if (c->tr_n > 0) c->tr_next = c->tr_stride;  // the tracers stay; their updates count from the new state
-    if (c->av_fields) c->av_next = c->av_stride;  // so do the averages: sums and counts kept, samples from the new state
+    c->tr_ev.arm(c->t);  // tracers stay; their updates count from the new state
+    c->av_ev.arm(c->t);  // so do the averages: sums and counts kept, samples from the new state
     return IBLB_OK;
 }
 
@@ -661,287 +634,6 @@ int iblb_set_cilia(iblb_ctx* c, const iblb_cilia* k) {
     return IBLB_OK;
 }
 
-int iblb_get_lagrangian(iblb_ctx* c, float* s, float* u_s, int* epsilon) {
-    if (!c) return IBLB_ERR_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const size_t ns = (size_t)c->ns;
-    if (ns == 0) return IBLB_OK;
-    if (s) HIP_TRY(c, hipMemcpy(s, pts_s(c), 2 * ns * sizeof(float), hipMemcpyDeviceToHost));
-    if (u_s) HIP_TRY(c, hipMemcpy(u_s, pts_us(c), 2 * ns * sizeof(float), hipMemcpyDeviceToHost));
-    if (epsilon) HIP_TRY(c, hipMemcpy(epsilon, pts_eps(c), ns * sizeof(int), hipMemcpyDeviceToHost));
-    return IBLB_OK;
-}
-
-int iblb_get_macro(iblb_ctx* c, double* rho, double* u) {
-    if (!c) return IBLB_ERR_ARG;
-    int rc = prepare_read(c);
-    if (rc) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const long N = (long)c->ncol * c->ny;
-    const size_t nb = (size_t)N * sizeof(double);
-    DevBuf d;
-    HIP_TRY(c, hipMalloc(&d.p, 3 * nb));
-    if ((rc = macro_device(c, (double*)d.p, (double*)d.p + N))) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (rho) HIP_TRY(c, hipMemcpy(rho, d.p, nb, hipMemcpyDeviceToHost));
-    if (u) HIP_TRY(c, hipMemcpy(u, (double*)d.p + N, 2 * nb, hipMemcpyDeviceToHost));
-    return IBLB_OK;
-}
-
-int iblb_get_populations(iblb_ctx* c, double* f) {
-    if (!c || !f) return IBLB_ERR_ARG;
-    int rc = prepare_read(c);
-    if (rc) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const long N = (long)c->ncol * c->ny;
-    DevBuf df;
-    HIP_TRY(c, hipMalloc(&df.p, 9 * (size_t)N * sizeof(double)));
-    const int raw = c->phase == PH_BOOT;  // f^0 is stored unstreamed
-    if (is_f64(c))
-        HIP_TRY(c, launch_pop_out<double>(gptr<double>(c, c->cur), c->L, halo_of<double>(c, c->cur), (double*)df.p, raw,
-                                          c->stream));
-    else
-        HIP_TRY(c, launch_pop_out<float>(gptr<float>(c, c->cur), c->L, halo_of<float>(c, c->cur), (double*)df.p, raw,
-                                         c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(f, df.p, 9 * (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
-    return IBLB_OK;
-}
-
-int iblb_get_force(iblb_ctx* c, double* force) {
-    if (!c || !force) return IBLB_ERR_ARG;
-    int rc = prepare_read(c);
-    if (rc) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const long N = (long)c->ncol * c->ny;
-    DevBuf d;
-    HIP_TRY(c, hipMalloc(&d.p, 2 * (size_t)N * sizeof(double)));
-    if (c->phase == PH_BOOT)
-        HIP_TRY(c, launch_field_out(c->force0, (double*)d.p, c->L, 2, c->fplane, c->coef.gx, c->coef.gy, c->stream));
-    else
-        HIP_TRY(c, launch_field_out(c->ib_state == IB_READY ? c->fdense : nullptr, (double*)d.p, c->L, 2, c->fplane,
-                                    c->coef.gx, c->coef.gy, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(force, d.p, 2 * (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
-    return IBLB_OK;
-}
-
-int iblb_get_lagrangian_force(iblb_ctx* c, float* F_s) {
-    if (!c || !F_s) return IBLB_ERR_ARG;
-    int rc = prepare_read(c);
-    if (rc) return rc;
-    if (c->ns == 0) return IBLB_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const float* src = c->d_Fs;
-    if (rccl_multi(c)) {  // each point's F_s is held by one slab, zeros elsewhere: sum exactly
-        if ((rc = rccl_order(c, c->stream))) return rc;
-        NCCL_TRY(c, ncclAllReduce(c->d_Fs, c->d_Fs_sum, 2 * (size_t)c->ns, ncclFloat32, ncclSum, c->comm, c->stream));
-        src = c->d_Fs_sum;
-    }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(F_s, src, 2 * (size_t)c->ns * sizeof(float), hipMemcpyDeviceToHost));
-    return IBLB_OK;
-}
-
-int iblb_get_flux(iblb_ctx* c, double* Q) {
-    if (!c || !Q) return IBLB_ERR_ARG;
-    int rc = prepare_read(c);
-    if (rc) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    // d_Q[1] = d_Q[0] + q(u^t) of the current (not yet collided) state
-    HIP_TRY(c, hipMemcpyAsync(c->d_Q + 1, c->d_Q, sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    const int fc = c->cfg.flux_column - c->x_begin;
-    if (c->phase == PH_RUN && fc >= 0 && fc < c->ncol) {
-        const double* fd = c->ib_state == IB_READY ? c->fdense : nullptr;
-        if (is_f64(c))
-            HIP_TRY(c, launch_flux<double>(gptr<double>(c, c->cur), c->L, halo_of<double>(c, c->cur), fd, c->fplane,
-                                           c->coef.gx, c->coef.gy, fc, c->cfg.flux_norm, c->d_Q + 1, c->stream));
-        else
-            HIP_TRY(c, launch_flux<float>(gptr<float>(c, c->cur), c->L, halo_of<float>(c, c->cur), fd, c->fplane,
-                                          c->coef.gx, c->coef.gy, fc, c->cfg.flux_norm, c->d_Q + 1, c->stream));
-    }
-    if (rccl_multi(c)) {
-        if ((rc = rccl_order(c, c->stream))) return rc;
-        NCCL_TRY(c, ncclAllReduce(c->d_Q + 1, c->d_Q + 1, 1, ncclFloat64, ncclSum, c->comm, c->stream));
-    }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(Q, c->d_Q + 1, sizeof(double), hipMemcpyDeviceToHost));
-    return IBLB_OK;
-}
-
-int iblb_count_nonfinite(iblb_ctx* c, long long* count) {
-    if (!c || !count) return IBLB_ERR_ARG;
-    int rc = check_ready(c);
-    if (rc) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if ((rc = band_join(c)) || (rc = join_comm(c))) return rc;
-    HIP_TRY(c, hipMemsetAsync(c->d_Q + 1, 0, sizeof(double), c->stream));
-    if (is_f64(c)) HIP_TRY(c, launch_count_nonfinite<double>(gptr<double>(c, c->cur), c->L, c->d_Q + 1, c->stream));
-    else HIP_TRY(c, launch_count_nonfinite<float>(gptr<float>(c, c->cur), c->L, c->d_Q + 1, c->stream));
-    if (rccl_multi(c)) {
-        if ((rc = rccl_order(c, c->stream))) return rc;
-        NCCL_TRY(c, ncclAllReduce(c->d_Q + 1, c->d_Q + 1, 1, ncclFloat64, ncclSum, c->comm, c->stream));
-    }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    double n = 0.;
-    HIP_TRY(c, hipMemcpy(&n, c->d_Q + 1, sizeof(double), hipMemcpyDeviceToHost));
-    *count = (long long)n;
-    return IBLB_OK;
-}
-
-// ---- windowed field readback ----------------------------------------------------------------------
-// The window (NULL: the whole lattice at stride 1) checked against the lattice, and the samples whose
-// column this slab owns: [*i_first, *i_first + *nxl) of the window's nx.
-static int window_part(iblb_ctx* c, const iblb_window* w, iblb_window* win, int* i_first, int* nxl) {
-    *win = w ? *w : iblb_window{0, 0, c->nx, c->ny, 1, 1};
-    if (win->sx < 1 || win->sy < 1 || win->nx < 1 || win->ny < 1 || win->x0 < 0 || win->y0 < 0 ||
-        (long long)win->x0 + (long long)(win->nx - 1) * win->sx >= c->nx ||
-        (long long)win->y0 + (long long)(win->ny - 1) * win->sy >= c->ny)
-        return fail(c, IBLB_ERR_ARG, "window: need sx, sy, nx, ny >= 1 and every sample inside the lattice (no wrap)");
-    // first sample at or right of x_begin, first sample at or right of the slab's end
-    auto first_at = [&](long long x) {
-        const long long i = x <= win->x0 ? 0 : (x - win->x0 + win->sx - 1) / win->sx;
-        return (int)std::min(i, (long long)win->nx);
-    };
-    const int lo = first_at(c->x_begin), hi = first_at((long long)c->x_begin + c->ncol);
-    *i_first = lo;
-    *nxl = hi - lo;
-    return IBLB_OK;
-}
-
-int iblb_window_local(iblb_ctx* c, const iblb_window* w, int* i_first, int* nx_local) {
-    if (!c) return IBLB_ERR_ARG;
-    iblb_window win;
-    int lo = 0, n = 0;
-    int rc = window_part(c, w, &win, &lo, &n);
-    if (rc) return rc;
-    if (i_first) *i_first = lo;
-    if (nx_local) *nx_local = n;
-    return IBLB_OK;
-}
-
-// The arguments of the windowed kernels for this slab's part of window win: samples [lo, lo + nxl)
-static FieldsArgs window_args(iblb_ctx* c, const iblb_window& win, int lo, int nxl, unsigned fields) {
-    FieldsArgs a{};
-    a.xl0 = win.x0 + lo * win.sx - c->x_begin;
-    a.sx = win.sx;
-    a.nxl = nxl;
-    a.y0 = win.y0;
-    a.sy = win.sy;
-    a.nyw = win.ny;
-    a.fields = fields;
-    a.fplane = c->fplane;
-    a.gx = c->coef.gx;
-    a.gy = c->coef.gy;
-    a.kvisc = -c->coef.kguo;
-    if (c->phase == PH_BOOT) {
-        a.rho0 = c->rho0;
-        a.u0 = c->u0;
-    } else {
-        a.fdense = c->ib_state == IB_READY ? c->fdense : nullptr;
-    }
-    return a;
-}
-
-int iblb_get_fields(iblb_ctx* c, const iblb_window* w, unsigned fields, double* out) {
-    if (!c) return IBLB_ERR_ARG;
-    const unsigned known = IBLB_FIELD_RHO | IBLB_FIELD_UX | IBLB_FIELD_UY | IBLB_FIELD_VORT | IBLB_FIELD_SXX |
-                           IBLB_FIELD_SXY | IBLB_FIELD_SYY;
-    if (fields == 0 || (fields & ~known)) return fail(c, IBLB_ERR_ARG, "fields: no field or an unknown IBLB_FIELD_* bit");
-    iblb_window win;
-    int lo = 0, nxl = 0;
-    int rc = window_part(c, w, &win, &lo, &nxl);
-    if (rc) return rc;
-    if (nxl > 0 && !out) return fail(c, IBLB_ERR_ARG, "out is NULL");
-    if ((fields & IBLB_FIELD_VORT) && !single_slab(c))
-        return fail(c, IBLB_ERR_UNSUPPORTED,
-                    "vorticity needs the neighbour slabs' velocity and force: a lone slab only (compute it from "
-                    "the gathered u)");
-    if ((rc = prepare_read(c))) return rc;
-    if (nxl == 0) return IBLB_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const int nf = __builtin_popcount(fields);
-    const size_t nb = (size_t)nf * win.ny * nxl * sizeof(double);
-    const FieldsArgs a = window_args(c, win, lo, nxl, fields);
-    DevBuf d;
-    HIP_TRY(c, hipMalloc(&d.p, nb));
-    if (is_f64(c))
-        HIP_TRY(c, launch_fields_out<double>(gptr<double>(c, c->cur), c->L, halo_of<double>(c, c->cur), a, (double*)d.p,
-                                             c->stream));
-    else
-        HIP_TRY(c, launch_fields_out<float>(gptr<float>(c, c->cur), c->L, halo_of<float>(c, c->cur), a, (double*)d.p,
-                                            c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(out, d.p, nb, hipMemcpyDeviceToHost));
-    return IBLB_OK;
-}
-
-// ---- window reduction ---------------------------------------------------------------------------------
-int iblb_reduce_fields(iblb_ctx* c, const iblb_window* w, unsigned fields, iblb_field_stats* stats, double* row_sum,
-                       double* col_sum) {
-    if (!c) return IBLB_ERR_ARG;
-    const unsigned known = IBLB_FIELD_RHO | IBLB_FIELD_UX | IBLB_FIELD_UY | IBLB_FIELD_VORT | IBLB_FIELD_SXX |
-                           IBLB_FIELD_SXY | IBLB_FIELD_SYY | IBLB_QTY_MOMX | IBLB_QTY_MOMY | IBLB_QTY_KE | IBLB_QTY_USQ;
-    if (fields == 0 || (fields & ~known))
-        return fail(c, IBLB_ERR_ARG, "fields: no quantity or an unknown IBLB_FIELD_* / IBLB_QTY_* bit");
-    iblb_window win;
-    int lo = 0, nxl = 0;
-    int rc = window_part(c, w, &win, &lo, &nxl);
-    if (rc) return rc;
-    if (!stats) return fail(c, IBLB_ERR_ARG, "stats is NULL");
-    if ((fields & IBLB_FIELD_VORT) && !single_slab(c))
-        return fail(c, IBLB_ERR_UNSUPPORTED,
-                    "vorticity needs the neighbour slabs' velocity and force: a lone slab only (compute it from "
-                    "the gathered u)");
-    if ((rc = prepare_read(c))) return rc;
-    const int nf = __builtin_popcount(fields);
-    if (nxl == 0) {  // none of the window's columns is this slab's
-        for (int k = 0; k < nf; ++k)
-            stats[k] = iblb_field_stats{0, 0, 0., 0., HUGE_VAL, -HUGE_VAL, -1, -1, -1, -1};
-        if (row_sum) std::fill(row_sum, row_sum + (size_t)nf * win.ny, 0.);
-        return IBLB_OK;
-    }
-    HIP_TRY(c, hipSetDevice(c->device));
-    ReduceGeom q = reduce_geometry(nxl, win.ny, nf, row_sum != nullptr, col_sum != nullptr);
-    q.i_first = lo;
-    if ((size_t)q.n_scratch > c->red_cap) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (c->red_buf) HIP_TRY(c, hipFree(c->red_buf));
-        c->red_buf = nullptr;
-        c->red_cap = 0;
-        if (hipMalloc((void**)&c->red_buf, (size_t)q.n_scratch * sizeof(double)) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(c, IBLB_ERR_NOMEM, "iblb_reduce_fields: scratch allocation failed");
-        }
-        c->red_cap = (size_t)q.n_scratch;
-    }
-    const FieldsArgs a = window_args(c, win, lo, nxl, fields);
-    if (is_f64(c))
-        HIP_TRY(c, launch_reduce_fields<double>(gptr<double>(c, c->cur), c->L, halo_of<double>(c, c->cur), a, q,
-                                                c->red_buf, c->stream));
-    else
-        HIP_TRY(c, launch_reduce_fields<float>(gptr<float>(c, c->cur), c->L, halo_of<float>(c, c->cur), a, q,
-                                               c->red_buf, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->red_host.resize((size_t)q.n_out);
-    HIP_TRY(c, hipMemcpy(c->red_host.data(), c->red_buf + q.o_out, (size_t)q.n_out * sizeof(double),
-                         hipMemcpyDeviceToHost));
-    const double* h = c->red_host.data();
-    for (int k = 0; k < nf; ++k) {
-        const double* r = h + (size_t)k * REDUCE_RS;
-        stats[k] = iblb_field_stats{(long long)r[0], (long long)r[1], r[2], r[3], r[4], r[5],
-                                    (int)r[6], (int)r[7], (int)r[8], (int)r[9]};
-    }
-    h += (size_t)nf * REDUCE_RS;
-    if (row_sum) {
-        std::copy(h, h + (size_t)nf * win.ny, row_sum);
-        h += (size_t)nf * win.ny;
-    }
-    if (col_sum) std::copy(h, h + (size_t)nf * nxl, col_sum);
-    return IBLB_OK;
-}
-
 int iblb_get_step(iblb_ctx* c, long long* steps) {
     if (!c || !steps) return IBLB_ERR_ARG;
     *steps = c->t;
@@ -1022,356 +714,6 @@ int iblb_synchronize(iblb_ctx* c) {
     for (hipStream_t s : {c->stream, c->comm_stream, c->band_st, c->deep_st})
         if (s) HIP_TRY(c, hipStreamSynchronize(s));
     return check_wait_err(c);
-}
-
-// ---- output gather (RCCL group) -----------------------------------------------------------------
-int iblb_gather_macro(iblb_ctx* c, int root, double* rho, double* u) {
-    if (!c) return IBLB_ERR_ARG;
-    if (c->transport == TR_LOCAL) return fail(c, IBLB_ERR_STATE, "local group: gather the slabs' iblb_get_macro");
-    if (!rccl_multi(c)) return iblb_get_macro(c, rho, u);
-    if (root < 0 || root >= c->nranks) return fail(c, IBLB_ERR_ARG, "root rank out of range");
-    int rc = prepare_read(c);
-    if (rc) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const long N = (long)c->ncol * c->ny;
-    DevBuf mine, all;
-    HIP_TRY(c, hipMalloc(&mine.p, 3 * (size_t)N * sizeof(double)));
-    if ((rc = macro_device(c, (double*)mine.p, (double*)mine.p + N))) return rc;
-    const bool is_root = c->rank == root;
-    const size_t total = 3 * (size_t)c->nx * c->ny;
-    if (is_root) HIP_TRY(c, hipMalloc(&all.p, total * sizeof(double)));
-    if ((rc = rccl_order(c, c->stream))) return rc;
-    // rank r's [rho | u] block lands at 3*ny*x_begin_r in rank order
-    NCCL_TRY(c, ncclGroupStart());
-    if (is_root) {
-        for (int r = 0; r < c->nranks; ++r) {
-            double* dst = (double*)all.p + 3L * c->ny * c->slab_begin[r];
-            const size_t n = 3 * (size_t)c->ny * c->slab_count[r];
-            if (r == root) HIP_TRY(c, hipMemcpyAsync(dst, mine.p, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-            else NCCL_TRY(c, ncclRecv(dst, n, ncclFloat64, r, c->comm, c->stream));
-        }
-    } else {
-        NCCL_TRY(c, ncclSend(mine.p, 3 * (size_t)N, ncclFloat64, root, c->comm, c->stream));
-    }
-    NCCL_TRY(c, ncclGroupEnd());
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (!is_root || (!rho && !u)) return IBLB_OK;
-    std::vector<double> h(total);
-    HIP_TRY(c, hipMemcpy(h.data(), all.p, total * sizeof(double), hipMemcpyDeviceToHost));
-    const long nx = c->nx, ny = c->ny, G = nx * ny;
-    for (int r = 0; r < c->nranks; ++r) {
-        const long xb = c->slab_begin[r], nc = c->slab_count[r], n = nc * ny;
-        const double* blk = h.data() + 3 * ny * xb;
-        for (long y = 0; y < ny; ++y)
-            for (long xc = 0; xc < nc; ++xc) {
-                const long j = y * nc + xc, g = y * nx + xb + xc;
-                if (rho) rho[g] = blk[j];
-                if (u) {
-                    u[g] = blk[n + j];
-                    u[G + g] = blk[2 * n + j];
-                }
-            }
-    }
-    return IBLB_OK;
-}
-
-}  // extern "C"
-
-// ---- point sampling and passive tracers -------------------------------------------------------------
-namespace iblbh {
-
-// The state-dependent part of the kernels' arguments (no window): what window_args gives every reader
-static FieldsArgs point_args(iblb_ctx* c, unsigned fields) {
-    return window_args(c, iblb_window{0, 0, 1, 1, 1, 1}, 0, 1, fields);
-}
-
-// Every position finite and inside [0, XDIM) x [0, YDIM-1]: the kernels index the lattice from them
-static int check_positions(iblb_ctx* c, long long n, const double* x, const double* y) {
-    if (c->ny < 2) return fail(c, IBLB_ERR_ARG, "bilinear sampling needs YDIM >= 2");
-    const double X = (double)c->nx, ytop = (double)(c->ny - 1);
-    for (long long p = 0; p < n; ++p)
-        if (!(std::isfinite(x[p]) && std::isfinite(y[p]) && x[p] >= 0. && x[p] < X && y[p] >= 0. && y[p] <= ytop))
-            return fail(c, IBLB_ERR_ARG,
-                        "point " + std::to_string(p) + " is non-finite or outside 0 <= x < XDIM, 0 <= y <= YDIM-1");
-    return IBLB_OK;
-}
-
-static int group_refused(iblb_ctx* c, const char* what) {
-    return fail(c, IBLB_ERR_UNSUPPORTED,
-                std::string(what) + ": a lone slab only (the four cells of a point may straddle the slabs of a group)");
-}
-
-static void tracers_free(iblb_ctx* c) {
-    for (void* p : {(void*)c->tr_x, (void*)c->tr_y, (void*)c->tr_laps})
-        if (p) (void)hipFree(p);
-    c->tr_x = c->tr_y = nullptr;
-    c->tr_laps = nullptr;
-    c->tr_n = 0;
-    c->tr_stride = 1;
-    c->tr_next = 0;
-    c->tr_updates = 0;
-}
-
-// One update of the tracers from the current state, on the context's stream: the state prepared as
-// for a reader (the band streams joined, the owed IB force evaluated), then one launch.
-int tracer_update(iblb_ctx* c) {
-    int rc = band_join(c);
-    if (rc || (rc = prepare_read(c))) return rc;
-    const FieldsArgs a = point_args(c, IBLB_FIELD_UX | IBLB_FIELD_UY);
-    if (is_f64(c))
-        HIP_TRY(c, launch_tracer_advect<double>(gptr<double>(c, c->cur), c->L, halo_of<double>(c, c->cur), a, (long)c->tr_n,
-                                                c->tr_stride, c->tr_x, c->tr_y, c->tr_laps, c->stream));
-    else
-        HIP_TRY(c, launch_tracer_advect<float>(gptr<float>(c, c->cur), c->L, halo_of<float>(c, c->cur), a, (long)c->tr_n,
-                                               c->tr_stride, c->tr_x, c->tr_y, c->tr_laps, c->stream));
-    c->tr_next += c->tr_stride;
-    c->tr_updates++;
-    return IBLB_OK;
-}
-
-}  // namespace iblbh
-
-extern "C" {
-
-int iblb_sample_points(iblb_ctx* c, int n, const double* x, const double* y, unsigned fields, double* out) {
-    if (!c) return IBLB_ERR_ARG;
-    const unsigned known = IBLB_FIELD_RHO | IBLB_FIELD_UX | IBLB_FIELD_UY | IBLB_FIELD_VORT | IBLB_FIELD_SXX |
-                           IBLB_FIELD_SXY | IBLB_FIELD_SYY;
-    if (n < 0) return fail(c, IBLB_ERR_ARG, "n is negative");
-    if (n > 0 && (!x || !y || !out)) return fail(c, IBLB_ERR_ARG, "x, y or out is NULL");
-    if (fields == 0 || (fields & ~known)) return fail(c, IBLB_ERR_ARG, "fields: no field or an unknown IBLB_FIELD_* bit");
-    if (!single_slab(c)) return group_refused(c, "iblb_sample_points");
-    int rc = check_positions(c, n, x, y);
-    if (rc) return rc;
-    if (n == 0) return IBLB_OK;
-    if ((rc = prepare_read(c))) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const int nf = __builtin_popcount(fields);
-    const size_t np = (size_t)n;
-    std::vector<double> xy(2 * np);  // one copy in: x then y
-    std::copy(x, x + np, xy.begin());
-    std::copy(y, y + np, xy.begin() + np);
-    DevBuf d_xy, d_out;
-    HIP_TRY(c, hipMalloc(&d_xy.p, 2 * np * sizeof(double)));
-    HIP_TRY(c, hipMalloc(&d_out.p, nf * np * sizeof(double)));
-    HIP_TRY(c, hipMemcpyAsync(d_xy.p, xy.data(), 2 * np * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    const FieldsArgs a = point_args(c, fields);
-    if (is_f64(c))
-        HIP_TRY(c, launch_sample_points<double>(gptr<double>(c, c->cur), c->L, halo_of<double>(c, c->cur), a, (long)n,
-                                                (const double*)d_xy.p, (double*)d_out.p, c->stream));
-    else
-        HIP_TRY(c, launch_sample_points<float>(gptr<float>(c, c->cur), c->L, halo_of<float>(c, c->cur), a, (long)n,
-                                               (const double*)d_xy.p, (double*)d_out.p, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(out, d_out.p, nf * np * sizeof(double), hipMemcpyDeviceToHost));
-    return IBLB_OK;
-}
-
-int iblb_set_tracers(iblb_ctx* c, long long n, const double* x, const double* y, int stride) {
-    if (!c) return IBLB_ERR_ARG;
-    if (n < 0) return fail(c, IBLB_ERR_ARG, "n is negative");
-    if (stride < 1) return fail(c, IBLB_ERR_ARG, "stride must be >= 1");
-    if (n > 0 && (!x || !y)) return fail(c, IBLB_ERR_ARG, "x or y is NULL");
-    if (!single_slab(c)) return group_refused(c, "iblb_set_tracers");
-    int rc = check_positions(c, n, x, y);
-    if (rc) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (n == 0) {
-        tracers_free(c);
-        return IBLB_OK;
-    }
-    // the new arrays first: a failed allocation leaves the previous tracers as they were
-    const size_t np = (size_t)n;
-    DevBuf dx, dy, dl;
-    HIP_TRY(c, hipMalloc(&dx.p, np * sizeof(double)));
-    HIP_TRY(c, hipMalloc(&dy.p, np * sizeof(double)));
-    HIP_TRY(c, hipMalloc(&dl.p, np * sizeof(int)));
-    HIP_TRY(c, hipMemcpy(dx.p, x, np * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(dy.p, y, np * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemsetAsync(dl.p, 0, np * sizeof(int), c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    tracers_free(c);
-    c->tr_x = (double*)dx.p;
-    c->tr_y = (double*)dy.p;
-    c->tr_laps = (int*)dl.p;
-    dx.p = dy.p = dl.p = nullptr;
-    c->tr_n = n;
-    c->tr_stride = stride;
-    c->tr_next = c->t + stride;
-    c->tr_updates = 0;
-    return IBLB_OK;
-}
-
-int iblb_get_tracers(iblb_ctx* c, double* x, double* y, int* laps) {
-    if (!c) return IBLB_ERR_ARG;
-    if (c->tr_n == 0) return IBLB_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const size_t np = (size_t)c->tr_n;
-    if (x) HIP_TRY(c, hipMemcpy(x, c->tr_x, np * sizeof(double), hipMemcpyDeviceToHost));
-    if (y) HIP_TRY(c, hipMemcpy(y, c->tr_y, np * sizeof(double), hipMemcpyDeviceToHost));
-    if (laps) HIP_TRY(c, hipMemcpy(laps, c->tr_laps, np * sizeof(int), hipMemcpyDeviceToHost));
-    return IBLB_OK;
-}
-
-int iblb_tracer_count(iblb_ctx* c, long long* n, int* stride, long long* updates) {
-    if (!c) return IBLB_ERR_ARG;
-    if (n) *n = c->tr_n;
-    if (stride) *stride = c->tr_stride;
-    if (updates) *updates = c->tr_updates;
-    return IBLB_OK;
-}
-
-}  // extern "C"
-
-// ---- time- and phase-averaged fields ----------------------------------------------------------------
-namespace iblbh {
-
-static void average_free(iblb_ctx* c) {
-    if (c->av_buf) (void)hipFree(c->av_buf);
-    c->av_buf = nullptr;
-    c->av_win = iblb_window{};
-    c->av_fields = c->av_flags = 0;
-    c->av_stride = c->av_nbins = 1;
-    c->av_planes = 0;
-    c->av_next = 0;
-    c->av_samples = 0;
-    c->av_count.clear();
-}
-
-static size_t average_bin_elems(const iblb_ctx* c) {
-    return (size_t)c->av_planes * (size_t)c->av_win.nx * (size_t)c->av_win.ny;
-}
-
-// One sample of the averaged fields from the current state, on the context's stream: the state prepared
-// as for a reader (the band streams joined, the owed IB force evaluated), then one launch.
-int average_update(iblb_ctx* c) {
-    if (!single_slab(c))  // the context joined a group after iblb_set_average: its window is the whole lattice's
-        return fail(c, IBLB_ERR_UNSUPPORTED, "averaging: a lone slab only; remove it before joining a group");
-    int rc = band_join(c);
-    if (rc || (rc = prepare_read(c))) return rc;
-    const int bin = (int)(c->av_samples % c->av_nbins);
-    const FieldsArgs a = window_args(c, c->av_win, 0, c->av_win.nx, c->av_fields);
-    double* acc = c->av_buf + (size_t)bin * average_bin_elems(c);
-    if (is_f64(c))
-        HIP_TRY(c, launch_average_accum<double>(gptr<double>(c, c->cur), c->L, halo_of<double>(c, c->cur), a, c->av_flags,
-                                                acc, c->stream));
-    else
-        HIP_TRY(c, launch_average_accum<float>(gptr<float>(c, c->cur), c->L, halo_of<float>(c, c->cur), a, c->av_flags, acc,
-                                               c->stream));
-    c->av_next += c->av_stride;
-    c->av_samples++;
-    c->av_count[bin]++;
-    return IBLB_OK;
-}
-
-}  // namespace iblbh
-
-extern "C" {
-
-int iblb_set_average(iblb_ctx* c, const iblb_window* w, unsigned fields, int stride, int nbins, unsigned flags) {
-    if (!c) return IBLB_ERR_ARG;
-    const unsigned known = IBLB_FIELD_RHO | IBLB_FIELD_UX | IBLB_FIELD_UY | IBLB_FIELD_VORT | IBLB_FIELD_SXX |
-                           IBLB_FIELD_SXY | IBLB_FIELD_SYY;
-    const bool remove = fields == 0 && !w;
-    if (!remove) {
-        if (fields == 0 || (fields & ~known)) return fail(c, IBLB_ERR_ARG, "fields: no field or an unknown IBLB_FIELD_* bit");
-        if (flags & ~(unsigned)(IBLB_AVG_SQ | IBLB_AVG_UXUY)) return fail(c, IBLB_ERR_ARG, "flags: an unknown IBLB_AVG_* bit");
-        if ((flags & IBLB_AVG_UXUY) && (fields & (IBLB_FIELD_UX | IBLB_FIELD_UY)) != (IBLB_FIELD_UX | IBLB_FIELD_UY))
-            return fail(c, IBLB_ERR_ARG, "IBLB_AVG_UXUY needs both IBLB_FIELD_UX and IBLB_FIELD_UY");
-        if (stride < 1) return fail(c, IBLB_ERR_ARG, "stride must be >= 1");
-        if (nbins < 1) return fail(c, IBLB_ERR_ARG, "nbins must be >= 1");
-    }
-    iblb_window win;
-    int lo = 0, nxl = 0;
-    int rc = window_part(c, w, &win, &lo, &nxl);
-    if (rc) return rc;
-    if (!single_slab(c))
-        return fail(c, IBLB_ERR_UNSUPPORTED,
-                    "iblb_set_average: a lone slab only (averaging on the slabs of a group is not built)");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (remove) {
-        average_free(c);
-        return IBLB_OK;
-    }
-    // the new accumulators first: a failed allocation leaves the previous set as it was
-    const int nf = __builtin_popcount(fields);
-    const int planes = nf * ((flags & IBLB_AVG_SQ) ? 2 : 1) + ((flags & IBLB_AVG_UXUY) ? 1 : 0);
-    const long long cells = (long long)win.nx * win.ny;  // at most the lattice's
-    if (cells > LLONG_MAX / (long long)sizeof(double) / planes / nbins)
-        return fail(c, IBLB_ERR_NOMEM, "iblb_set_average: the accumulators exceed the address space");
-    const size_t bytes = (size_t)cells * planes * nbins * sizeof(double);
-    DevBuf d;
-    HIP_TRY(c, hipMalloc(&d.p, bytes));
-    HIP_TRY(c, hipMemsetAsync(d.p, 0, bytes, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    average_free(c);
-    c->av_buf = (double*)d.p;
-    d.p = nullptr;
-    c->av_win = win;
-    c->av_fields = fields;
-    c->av_flags = flags;
-    c->av_stride = stride;
-    c->av_nbins = nbins;
-    c->av_planes = planes;
-    c->av_next = c->t + stride;
-    c->av_samples = 0;
-    c->av_count.assign((size_t)nbins, 0);
-    return IBLB_OK;
-}
-
-int iblb_reset_average(iblb_ctx* c) {
-    if (!c) return IBLB_ERR_ARG;
-    if (!c->av_fields) return fail(c, IBLB_ERR_STATE, "iblb_reset_average: no averaging is set");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemsetAsync(c->av_buf, 0, (size_t)c->av_nbins * average_bin_elems(c) * sizeof(double), c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->av_next = c->t + c->av_stride;
-    c->av_samples = 0;
-    c->av_count.assign((size_t)c->av_nbins, 0);
-    return IBLB_OK;
-}
-
-int iblb_get_average(iblb_ctx* c, int bin, double* sum, double* sum_sq, double* sum_uxuy, long long* samples) {
-    if (!c) return IBLB_ERR_ARG;
-    if (!c->av_fields) return fail(c, IBLB_ERR_STATE, "iblb_get_average: no averaging is set");
-    if (bin < 0 || bin >= c->av_nbins) return fail(c, IBLB_ERR_ARG, "bin is outside [0, nbins)");
-    if (sum_sq && !(c->av_flags & IBLB_AVG_SQ)) return fail(c, IBLB_ERR_ARG, "sum_sq was not requested (IBLB_AVG_SQ)");
-    if (sum_uxuy && !(c->av_flags & IBLB_AVG_UXUY))
-        return fail(c, IBLB_ERR_ARG, "sum_uxuy was not requested (IBLB_AVG_UXUY)");
-    if (sum || sum_sq || sum_uxuy) {
-        HIP_TRY(c, hipSetDevice(c->device));
-        // the whole bin transposed into the ABI's layout on the device, then whole planes copied
-        const size_t plane = (size_t)c->av_win.nx * c->av_win.ny, n = average_bin_elems(c);
-        const int nf = __builtin_popcount(c->av_fields);
-        DevBuf d;
-        HIP_TRY(c, hipMalloc(&d.p, n * sizeof(double)));
-        HIP_TRY(c, launch_average_readout(c->av_buf + (size_t)bin * n, c->av_win.nx, c->av_win.ny, c->av_planes,
-                                          (double*)d.p, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        const double* t = (const double*)d.p;
-        if (sum) HIP_TRY(c, hipMemcpy(sum, t, nf * plane * sizeof(double), hipMemcpyDeviceToHost));
-        if (sum_sq) HIP_TRY(c, hipMemcpy(sum_sq, t + nf * plane, nf * plane * sizeof(double), hipMemcpyDeviceToHost));
-        if (sum_uxuy)
-            HIP_TRY(c, hipMemcpy(sum_uxuy, t + (size_t)(c->av_planes - 1) * plane, plane * sizeof(double),
-                                 hipMemcpyDeviceToHost));
-    }
-    if (samples) *samples = c->av_count[(size_t)bin];
-    return IBLB_OK;
-}
-
-int iblb_average_info(iblb_ctx* c, iblb_window* w, unsigned* fields, int* stride, int* nbins, unsigned* flags,
-                      long long* samples_total) {
-    if (!c) return IBLB_ERR_ARG;
-    if (w) *w = c->av_win;
-    if (fields) *fields = c->av_fields;
-    if (stride) *stride = c->av_stride;
-    if (nbins) *nbins = c->av_nbins;
-    if (flags) *flags = c->av_flags;
-    if (samples_total) *samples_total = c->av_samples;
-    return IBLB_OK;
 }
 
 }  // extern "C"

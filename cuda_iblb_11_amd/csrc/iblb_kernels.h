@@ -1,4 +1,4 @@
-// iblb_kernels.h — host-callable launchers of the slab kernels (used by iblb_ctx.hip).
+// iblb_kernels.h — host-callable launchers of the slab kernels (used by the ctx_*.hip files and iblb_ctx.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
