@@ -761,6 +761,25 @@ __device__ __forceinline__ typename VT<T, VS>::type lds_pop_read(const typename 
     return v;
 }
 
+// Stores in flight across the step boundary (round 8; f64 UL walks, one wave per SIMD).  A step issues the
+// next column's 9 loads after level 1 and level K's 9 stores at its end; the next step's level 1 waits
+// for the loads with a counted vmcnt, and memory operations are reported to the wave in issue order.  With
+// the stores under `made && keep` the paths into that wait carry 9 or 18 operations, the compiler takes
+// the smaller count, and on the storing path "load j landed" became vmcnt(8 - j): every step drained its
+// own stores, a write-acknowledge round trip with the SIMD idle.  So every step, and the walk's
+// prologue, issues exactly nine stores; the ones with nothing to write (a window-filling step, a lane
+// that owns no row) go to voffset BUF_DROP, beyond the column resource's num_records, where the buffer
+// range check discards them per lane (voffset + instruction offset is what it tests, not soffset), and
+// they still count in vmcnt.  The waits become vmcnt(9 + ...) and the stores drain under the next step.
+// BUF_DROP is 16-byte aligned and no sum with the vector's 16 bytes wraps 32 bits.
+// M f64 +3.0 %.  Not in the f32 window walks (three waves per SIMD
+// cover a wave's drain; not measured), and not in the f64 one-cell wall walks: built the same way (their
+// loads unconditional too, waits vmcnt(9) and up, same registers) they made M 0.1-1.2 % slower than the
+// inner walks alone in each of 12 alternations (profiles/r08/ab_m*).
+constexpr unsigned BUF_DROP = 0x80000000u;
+template <typename T, bool UL>
+constexpr bool store_in_flight() { return UL && sizeof(T) == 8; }
+
 // UL (the LDS-window walks, round 6): the next column's loads are unconditional, the last step loading
 // columns it already read (x - DX .. x + DX: inside the walk's reach): the loaded column then needs no
 // select against the old one at the loop's back edge (18 v_mov_b64 per f64 step)
@@ -772,6 +791,7 @@ __device__ __forceinline__ void sweepk_iter(const Sweep2Args<T>& a, int i, int n
                                             __amdgpu_buffer_rsrc_t (&rc)[3], bool fin, int fi, int fown, SkipState& sp,
                                             T* lw, ColPtrs<T>& cp) {
     constexpr int DX = REV ? -1 : 1;
+    constexpr bool SF = store_in_flight<T, UL>();
     const int x = x0 + i * DX;
     if constexpr (UL) cp.pd += DX * (long)a.L.col;  // output column x - (K-1) DX
     T N[9][VS];
@@ -850,10 +870,13 @@ __device__ __forceinline__ void sweepk_iter(const Sweep2Args<T>& a, int i, int n
         bool keep = owner;
         if constexpr ((MODE & MODE_SKIP) != 0)
             if (made && l == K) keep = owner && !skip_rows<T, VS, REV>(a, c, r0, sp);
-        if (made && l == K && keep) {
+        // SF: the nine stores are issued on every step, as dropped ones where the step makes no output column
+        // or the lane owns no row (store_in_flight)
+        if (SF ? l == K : (made && l == K && keep)) {
             const __amdgpu_buffer_rsrc_t rd = col_rsrc<T>(UL ? cp.pd : a.dst + (long)c * a.L.col);
+            const unsigned vo = (!SF || (made && keep)) ? bo.lane : BUF_DROP;
 #pragma unroll
-            for (int k = 0; k < 9; ++k) st_rows_buf<T, VS, MODE>(rd, bo.lane, (unsigned)k * bo.plane, out[k]);
+            for (int k = 0; k < 9; ++k) st_rows_buf<T, VS, MODE>(rd, vo, (unsigned)k * bo.plane, out[k]);
         }
         if constexpr (LW) {
             int p = 0;
@@ -959,6 +982,11 @@ __device__ __forceinline__ double sweepk_walk(const Sweep2Args<T>& a, int xa, in
     // (round 6 also tried two steps per trip with WA and WB swapping roles, the window's rotation a
     // renaming: the compiler kept the windows in AGPRs, 1399 instructions per f64 step against 1392)
     constexpr bool LW = lds_window<T, VS, MODE, WL>();
+    if constexpr (store_in_flight<T, LW>()) {  // the first step meets the count every later one does
+        const __amdgpu_buffer_rsrc_t rd = col_rsrc<T>(cp.pd);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) st_rows_buf<T, VS, MODE>(rd, BUF_DROP, (unsigned)k * bo.plane, WA[0][0]);
+    }
     for (int i = 0; i < nl1; ++i)
         sweepk_iter<T, VS, MODE, K, SLAB, REV, LW, LW>(a, i, nl1, x0, xa, xb, row0, off, lane, r0, et, owner, bot, top, walls,
                                                        WA, WB, cur, q, bo, rc, fin, fi, fown, sp, lw, cp);
