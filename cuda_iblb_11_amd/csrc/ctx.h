@@ -157,6 +157,9 @@ struct iblb_ctx {
     int* band_tab = nullptr;     // the installed plan's level tables (a pinned slot)
     bool band_run = false;       // the last step was a band cycle on band_st / deep_st (not joined)
     long long band_retry_t = 0;  // a declined schedule plan: next attempt at this iteration
+    long long band_hold_t = -1;  // the points were replaced (iblb_set_lagrangian, iblb_set_cilia) with the old points'
+                                 // force^t in the dense buffer, outside any plan of the new points: iteration
+                                 // band_hold_t is a one-step iteration (it consumes the force over the whole slab)
     hipEvent_t band_end = nullptr; // recorded on the deep stream at the end of the last band cycle
     char* s_alloc = nullptr;     // two scratch population buffers of the trapezoid (layout of g)
     void* sbuf[2] = {nullptr, nullptr};

@@ -652,6 +652,13 @@ static int step_range(iblb_ctx* c, int nsteps) {
     int rc = IBLB_OK;
     const int K = c->sweep_depth;
     for (int s = 0; s < nsteps;) {
+        if (c->t == c->band_hold_t && c->phase == PH_RUN) {
+            // force^t is that of points since replaced: outside the new points' band plan, where the cycle's
+            // deep sweep applies no IB force.  A one-step iteration consumes it over the whole slab
+            if ((rc = band_join(c)) || (rc = step_one(c))) return rc;
+            ++s;
+            continue;
+        }
         if (nsteps - s >= K && c->phase == PH_RUN && (!c->cilia_on || c->cil_sched) && K >= 3) {
             // a schedule's cycle whose plan was declined (trapezoids over half the lattice) is
             // planned again K iterations later, not at every one-step iteration in between

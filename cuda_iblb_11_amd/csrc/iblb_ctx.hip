@@ -529,6 +529,7 @@ int iblb_set_state(iblb_ctx* c, const double* rho, const double* u, const double
     }
     c->phase = PH_BOOT;
     c->t = 0;
+    c->band_hold_t = -1;
     c->ib_state = IB_NONE;
     c->ghost = 0;
     c->bnd_w = INT_MAX;
@@ -546,6 +547,8 @@ int iblb_set_lagrangian(iblb_ctx* c, int ns, const float* s, const float* u_s, c
     if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     if ((rc = retire_points(c))) return rc;  // force^t still owed to the old points
+    // ... and now in the dense buffer at the old points' cells: a band plan of the new points does not cover it
+    if (c->ns > 0 && c->ib_state == IB_READY) c->band_hold_t = c->t;
     if (ns > 0) {
         HIP_TRY(c, hipMemcpyAsync(c->d_s, s, 2 * (size_t)ns * sizeof(float), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipMemcpyAsync(c->d_us, u_s, 2 * (size_t)ns * sizeof(float), hipMemcpyHostToDevice, c->stream));
@@ -610,6 +613,7 @@ int iblb_set_cilia(iblb_ctx* c, const iblb_cilia* k) {
     int rc;
     if (c->phase == PH_RUN || c->ib_state == IB_PENDING) {
         if ((rc = retire_points(c))) return rc;  // force still owed to the current points
+        if (c->ns > 0 && c->ib_state == IB_READY) c->band_hold_t = c->t;  // (as in iblb_set_lagrangian)
     }
     c->band_valid = false;  // the points now come from the kinematics
     c->band_dirty = false;
@@ -866,6 +870,7 @@ int iblb_load_checkpoint(iblb_ctx* c, const char* path) {
     c->band_sticky = false;
     c->band_valid = false;
     c->band_retry_t = 0;
+    c->band_hold_t = -1;
     c->pts_host.clear();
     if (ns > 0 && !c->cilia_on) {  // host copy for the band plan of the restored points
         c->pts_host.resize(2 * ns);

@@ -192,7 +192,10 @@ int iblb_set_state(iblb_ctx* ctx, const double* rho, const double* u, const doub
 /* Lagrangian points for the next immersed-boundary evaluation (main.cu:834 boundary_check
  * outputs): s [2ns] xy, u_s [2ns] xy, epsilon [ns] (NULL = all 1).  Global coordinates.
  * A slab of a group needs >= 3 columns and the reference's invariant 0 <= s_x <= XDIM
- * (boundary_check wraps s_x into it, main.cu:202-205); IBLB_ERR_ARG otherwise. */
+ * (boundary_check wraps s_x into it, main.cu:202-205); IBLB_ERR_ARG otherwise.
+ * Points replaced in mid-run still owe their force to the next iteration: it is evaluated
+ * before the new points are taken, and the next iblb_step starts with a one-step iteration
+ * that applies it (then band cycles again). */
 int iblb_set_lagrangian(iblb_ctx* ctx, int ns, const float* s, const float* u_s,
                         const int* epsilon);
 
@@ -212,7 +215,13 @@ int iblb_set_lagrangian_steps(iblb_ctx* ctx, int nsteps, int ns, const float* s,
 /* On-device cilia kinematics (main.cu:822-841): when set, every iblb_step iteration `it`
  * first runs define_filament + boundary_check for `it` and uses their s, u_s, epsilon as the
  * Lagrangian points of that iteration (no host round trip).  c_num <= 0 or NULL disables.
- * Needs max_points >= 96 * c_num.  Excludes iblb_set_lagrangian while active. */
+ * Needs max_points >= 96 * c_num.  Excludes iblb_set_lagrangian while active.
+ * The kinematics start at the context's current iteration with zeroed history (the reference's
+ * `lasts`), and u_s is the displacement since the previous iteration: that gives a meaningful
+ * u_s only from iteration 0 (u_s(0) = 0 exactly), so set the cilia before the state, or at
+ * iteration 0.  A fresh start at it = 7 gives |u_s| of about 234 lattice units per iteration
+ * for that one iteration.  iblb_set_state restarts the beat (history zeroed, it = 0);
+ * a checkpoint holds the configuration and the history. */
 typedef struct iblb_cilia {
     int    c_num;    /* cilia (main.cu:268)                                        */
     double c_space;  /* spacing of the cilium bases in lattice units (main.cu:280) */

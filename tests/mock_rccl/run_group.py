@@ -8,6 +8,9 @@ usage: run_group.py NRANKS NX NY STEPS WITH_IB(0/1/2/3) PRECISION(f64/f32) [BULK
 
 BULK=1 (no IB): the group advances in multi-step calls (two-iteration sweeps with the 2-step
 halo, one-step launches for odd remainders) instead of one iteration per call.
+
+The points here are static or given ahead; the on-device cilia (iblb_set_cilia) on group slabs have
+a runner of their own, run_cilia.py.
 """
 import json
 import os
