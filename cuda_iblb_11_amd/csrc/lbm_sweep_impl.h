@@ -780,17 +780,36 @@ constexpr unsigned BUF_DROP = 0x80000000u;
 template <typename T, bool UL>
 constexpr bool store_in_flight() { return UL && sizeof(T) == 8; }
 
+// Step ranges (round 9; the f64 LDS-window walks).  `made` is false only on the first 2(K-1) steps of a
+// walk and the flux test true only on the K steps at which some level stands on the flux column, yet both
+// sat in every step as uniform branches: at K = 7 six `made` tests cut the step into seven basic blocks,
+// with their compares and branches, 11 s_waitcnt and SGPR-spill reloads (the 48 v_mov_b64 of phi copies
+// at the joins stand on the skipped arms: a steady step never ran them).  At one wave per SIMD every
+// such instruction costs its own issue slot.  So the walk runs its filling steps and its flux steps
+// through the general iteration and every other step through the STEADY one (sweepk_iter), one block.
+// The walks that have them need no NOFLUX build: the sweep that holds the flux column runs the same
+// steady loop as the others.
+// Not in the SLAB builds: there the two loops of each of the four window walks (plain and write-through,
+// forward and reverse) spill 46 more SGPRs over the kernel (223 -> 269), a fifth VGPR of spill lanes (243
+// -> 244 registers), and the build the context selects is pinned by its register count
+// (tests/test_gpu_fused.py:test_default_deep_builds).  Their steady loops were 1,197-1,209 instructions.
+template <typename T, int VS, int MODE, bool WL, bool SLAB>
+constexpr bool step_ranges() { return lds_window<T, VS, MODE, WL>() && sizeof(T) == 8 && !SLAB; }
+
 // UL (the LDS-window walks, round 6): the next column's loads are unconditional, the last step loading
 // columns it already read (x - DX .. x + DX: inside the walk's reach): the loaded column then needs no
 // select against the old one at the loop's back edge (18 v_mov_b64 per f64 step)
-template <typename T, int VS, int MODE, int K, bool SLAB, bool REV, bool LW, bool UL = false>
+// STEADY (round 9; the walk's step ranges, sweepk_walk): a step on which every level is made and none stands
+// on the flux column: no `made` test, no flux test, the step one basic block.
+template <typename T, int VS, int MODE, int K, bool SLAB, bool REV, bool LW, bool UL = false, bool STEADY = false>
 __device__ __forceinline__ void sweepk_iter(const Sweep2Args<T>& a, int i, int nl1, int x0, int xa, int xb, int row0,
                                             unsigned off, int lane, int r0, int et, bool owner, bool bot, bool top,
                                             bool walls, T (&WA)[K - 1][9][VS], T (&WB)[K - 1][9][VS],
                                             Raw<T, VS>& cur, double& q, const BufOfs& bo,
-                                            __amdgpu_buffer_rsrc_t (&rc)[3], bool fin, int fi, int fown, SkipState& sp,
+                                            __amdgpu_buffer_rsrc_t (&rc)[3], bool fin_, int fi, int fown, SkipState& sp,
                                             T* lw, ColPtrs<T>& cp) {
     constexpr int DX = REV ? -1 : 1;
+    const bool fin = !STEADY && fin_;
     constexpr bool SF = store_in_flight<T, UL>();
     const int x = x0 + i * DX;
     if constexpr (UL) cp.pd += DX * (long)a.L.col;  // output column x - (K-1) DX
@@ -840,13 +859,18 @@ __device__ __forceinline__ void sweepk_iter(const Sweep2Args<T>& a, int i, int n
             rc[0] = rn;
         }
         load_raw_periodic<T, VS, MODE, SLAB, K>(a, xl + DX, row0, off, bot, top, cur, bo, rc);
+        // The steady step is one scheduling region, and in it the scheduler sinks these loads towards the
+        // step's end to shorten their registers' lives (the reverse walk's last two stood 70 instructions
+        // before the next step's wait for them: M 3 % slower than the branching step).  Nothing crosses: the
+        // loads are issued with level 1, as the block boundary after level 1 had it.
+        if constexpr (STEADY) __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
     for (int l = 2; l <= K; ++l) {
         const int c = x - (l - 1) * DX;
         const bool flux = fin && i == fi + l - 1;
         T out[9][VS];
-        const bool made = i >= 2 * (l - 1);
+        const bool made = STEADY || i >= 2 * (l - 1);
         vec* ls = nullptr;
         if constexpr (LW) {  // slot of parity i: the column made two iterations ago, then this one's
             ls = lds_slot(l);
@@ -968,8 +992,9 @@ __device__ __forceinline__ double sweepk_walk(const Sweep2Args<T>& a, int xa, in
     int fown = 0;
 #pragma unroll
     for (int e = 0; e < VS; ++e) fown |= (owner && flux_row(a, r0 + e)) ? 1 << e : 0;
-    // (a main loop without the per-level `made` checks, after 2(K-1) window-filling iterations,
-    // lets the compiler hoist the collide constants into registers: VGPR spills, 512 VGPRs)
+    // (round 2, the register-window walks: a main loop without the per-level `made` checks, after 2(K-1)
+    // window-filling iterations, let the compiler hoist the collide constants into registers: VGPR
+    // spills, 512 VGPRs.  The f64 LDS-window walks of rounds 6-8 do not show it: step_ranges)
     SkipState sp{0, INT_MAX, INT_MIN, false};  // MODE_SKIP: the first region not left of the sweep (REV: right)
     if constexpr ((MODE & MODE_SKIP) != 0) {
         if (!REV)
@@ -987,9 +1012,40 @@ __device__ __forceinline__ double sweepk_walk(const Sweep2Args<T>& a, int xa, in
 #pragma unroll
         for (int k = 0; k < 9; ++k) st_rows_buf<T, VS, MODE>(rd, BUF_DROP, (unsigned)k * bo.plane, WA[0][0]);
     }
-    for (int i = 0; i < nl1; ++i)
-        sweepk_iter<T, VS, MODE, K, SLAB, REV, LW, LW>(a, i, nl1, x0, xa, xb, row0, off, lane, r0, et, owner, bot, top, walls,
-                                                       WA, WB, cur, q, bo, rc, fin, fi, fown, sp, lw, cp);
+    if constexpr (step_ranges<T, VS, MODE, WL, SLAB>()) {
+        // With g0 = 2(K-1) filling steps and the flux steps [fx, fx + K) (K-1 <= fx, fx + K <= nl1; none:
+        // fx beyond every step): general steps [0, g0) and [max(fx, g0), fx + K), steady steps every other;
+        // a range may be empty.  Each loop body is emitted once: at most two (general, steady) trips.  Only
+        // i, fx and nl1 name the ranges, and the flux sum goes to a.Q after each general range past fx (the
+        // kernel adds what the walk's last range leaves), so the steady loop keeps neither the range bounds
+        // nor q live (with the bounds in registers and q kept to the walk's end the lone K = 7 kernel took 264
+        // registers instead of 258, with four v_accvgpr_read per reverse step).
+        const int fx = fin ? fi : 1 << 30;
+        int i = 0, ge = min(nl1, 2 * (K - 1));
+#pragma clang loop unroll(disable)
+        for (;;) {
+            for (; i < ge; ++i)
+                sweepk_iter<T, VS, MODE, K, SLAB, REV, LW, LW>(a, i, nl1, x0, xa, xb, row0, off, lane, r0, et, owner, bot, top,
+                                                               walls, WA, WB, cur, q, bo, rc, true, fx, fown, sp, lw, cp);
+            if (i >= nl1) break;
+            if (i > fx) {  // (before the first flux step q is zero)
+                const double qs = wave_sum(q);
+                if (lane == 0) atomicAdd(a.Q, qs);
+            }
+            q = 0.;
+            const int se = i >= fx + K ? nl1 : min(max(fx, i), nl1);
+            for (; i < se; ++i)
+                sweepk_iter<T, VS, MODE, K, SLAB, REV, LW, LW, true>(a, i, nl1, x0, xa, xb, row0, off, lane, r0, et, owner, bot,
+                                                                     top, walls, WA, WB, cur, q, bo, rc, false, fx, fown, sp, lw,
+                                                                     cp);
+            if (i >= nl1) break;
+            ge = fx + K;
+        }
+    } else {
+        for (int i = 0; i < nl1; ++i)
+            sweepk_iter<T, VS, MODE, K, SLAB, REV, LW, LW>(a, i, nl1, x0, xa, xb, row0, off, lane, r0, et, owner, bot, top, walls,
+                                                           WA, WB, cur, q, bo, rc, fin, fi, fown, sp, lw, cp);
+    }
     return q;
 }
 
@@ -1154,7 +1210,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
                 goto walked;
             }
         }
-        if (sizeof(T) == 4 || (a.flux_col >= 0 && a.flux_col >= xa && a.flux_col < xb))  // (f32: spills 20 B)
+        // (f32: the flux-free walk spills 20 B; the walks in step ranges have no flux-free build)
+        if (step_ranges<T, VS, MODE, false, SLAB>() || sizeof(T) == 4 || (a.flux_col >= 0 && a.flux_col >= xa && a.flux_col < xb))
             q = rev ? sweepk_walk<T, VS, MODE, K, SLAB, true, false>(a, xa, xb, row0, off, lane, r0, et, owner, false, false, lw)
                     : sweepk_walk<T, VS, MODE, K, SLAB, false, false>(a, xa, xb, row0, off, lane, r0, et, owner, false, false, lw);
         else
