@@ -89,6 +89,14 @@ QUANTITIES = {**FIELDS, "momx": 128, "momy": 256, "ke": 512, "usq": 1024}
 # flags of iblb_set_average
 AVG_SQ = 1
 AVG_UXUY = 2
+# wall kinds of iblb_set_scalar
+SCALAR_WALL_NOFLUX = 0
+SCALAR_WALL_VALUE = 1
+
+
+class Scalar(C.Structure):
+    """struct iblb_scalar (include/iblb.h)."""
+    _fields_ = [("tau", C.c_double), ("stride", C.c_int), ("wall_kind", C.c_int * 2), ("wall_value", C.c_double * 2)]
 
 
 class FieldStats(C.Structure):
@@ -148,6 +156,10 @@ _SIGS = {
     "iblb_get_average": ([_vp, C.c_int, _vp, _vp, _vp, C.POINTER(C.c_longlong)], C.c_int),
     "iblb_average_info": ([_vp, C.POINTER(Window), C.POINTER(C.c_uint), C.POINTER(C.c_int), C.POINTER(C.c_int),
                            C.POINTER(C.c_uint), C.POINTER(C.c_longlong)], C.c_int),
+    "iblb_set_scalar": ([_vp, C.POINTER(Scalar), _vp, _vp], C.c_int),
+    "iblb_get_scalar": ([_vp, C.POINTER(Window), _vp], C.c_int),
+    "iblb_get_scalar_populations": ([_vp, _vp], C.c_int),
+    "iblb_scalar_info": ([_vp, C.POINTER(Scalar), C.POINTER(C.c_longlong)], C.c_int),
     "iblb_set_profiling": ([_vp, C.c_int], C.c_int),
     "iblb_get_timing": ([_vp, C.POINTER(Timing), C.c_int], C.c_int),
     "iblb_get_timing_ex": ([_vp, C.POINTER(Timing), C.c_ulong, C.c_int], C.c_int),

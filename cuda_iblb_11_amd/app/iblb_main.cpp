@@ -35,6 +35,11 @@
 // cov = sum_uxuy/n - mean_ux mean_uy; a blank line after each window row; a bin with n == 0 writes nothing.  It then
 // calls iblb_reset_average: each file is the average over the preceding output interval (the first file: from the
 // run's first iteration).  Checkpoints hold no averages: a restarted run starts them again.
+// IBLB_SCALAR=tau[,stride[,sx[,sy]]] (one GPU) lets the context advect and diffuse a passive scalar (iblb_set_scalar,
+// D = (tau - 0.5)/3, `stride` substeps every `stride` iterations, default 1) seeded C = 1 for y < YDIM/2 and 0 above,
+// no flux through the walls, and writes <it>-scalar.dat beside the fluid files at every output iteration (BigData or
+// not): one line  x  y  c  per sample of every sx-th column and sy-th row (default 1), lattice units, %.17g.
+// Checkpoints hold no scalar: a restarted run seeds it again.
 #include <sys/stat.h>
 #include <sys/time.h>
 #include <unistd.h>
@@ -251,6 +256,36 @@ int main(int argc, char* argv[]) {
         }
     }
 
+    // passive scalar (extension): relaxation time, 0 = off
+    double sc_tau = 0.;
+    int sc_stride = 1, sc_sx = 1, sc_sy = 1;
+    if (const char* ss = getenv("IBLB_SCALAR"); ss && *ss) {
+        // a number > 0.5, then up to three integers >= 1, separated by commas, nothing else
+        int* const dst[3] = {&sc_stride, &sc_sx, &sc_sy};
+        char* end = nullptr;
+        errno = 0;
+        sc_tau = strtod(ss, &end);
+        bool ok = ((*ss >= '0' && *ss <= '9') || *ss == '.') && end != ss && errno == 0 && std::isfinite(sc_tau) &&
+                  sc_tau > 0.5 && (*end == ',' || *end == 0);
+        for (int n = 0; ok && *end == ','; ++n) {
+            const char* p = end + 1;
+            errno = 0;
+            const long v = strtol(p, &end, 10);
+            ok = n < 3 && *p >= '0' && *p <= '9' && errno == 0 && v >= 1 && v <= 1000000000L && (*end == ',' || *end == 0);
+            if (ok) *dst[n] = (int)v;
+        }
+        if (!ok) {
+            if (lead)
+                cerr << "IBLB_SCALAR must be tau[,stride[,sx[,sy]]] with tau > 0.5 and every other value an integer >= 1, got "
+                     << ss << endl;
+            return 2;
+        }
+        if (world > 1) {  // the scalar on the slabs of a group is not built: a lone slab only (include/iblb.h)
+            if (lead) cerr << "IBLB_SCALAR is not available under a launcher (WORLD_SIZE > 1): run on one GPU" << endl;
+            return 2;
+        }
+    }
+
     const double dx = 1. / LENGTH;
     const double dt = 1. / (T);
     const double SPEED = 0.8 * 1000 / T;
@@ -343,6 +378,16 @@ int main(int argc, char* argv[]) {
         (rc = iblb_set_average(ctx, &av_win, IBLB_FIELD_RHO | IBLB_FIELD_UX | IBLB_FIELD_UY, av_stride, av_nbins,
                                IBLB_AVG_SQ | IBLB_AVG_UXUY)))
         return die(ctx, rc, "iblb_set_average");
+    // the scalar: C = 1 in the lower half of the channel, 0 above, no flux through the walls, from the run's first
+    // iteration (a restarted run's too: checkpoints hold no scalar)
+    iblb_window sc_win{0, 0, ((int)XDIM - 1) / sc_sx + 1, ((int)YDIM - 1) / sc_sy + 1, sc_sx, sc_sy};
+    std::vector<double> sc_out(sc_tau > 0. ? (size_t)sc_win.nx * sc_win.ny : 0);
+    if (sc_tau > 0.) {
+        std::vector<double> c0((size_t)size);
+        for (int j = 0; j < size; j++) c0[j] = (unsigned int)j / XDIM < YDIM / 2 ? 1. : 0.;
+        iblb_scalar sk{sc_tau, sc_stride, {IBLB_SCALAR_WALL_NOFLUX, IBLB_SCALAR_WALL_NOFLUX}, {0., 0.}};
+        if ((rc = iblb_set_scalar(ctx, &sk, c0.data(), nullptr))) return die(ctx, rc, "iblb_set_scalar");
+    }
 
     //----------------------------------------DEFINE DIRECTORIES---------------------------------- (main.cu:589-631)
     std::string output_data = env_str("IBLB_DATA_DIR", "Data/");
@@ -516,6 +561,19 @@ int main(int argc, char* argv[]) {
                 }
                 for (size_t k = 0; k < tr_n; k++) fprintf(ft, "%.17g\t%.17g\t%d\n", tr_x[k], tr_y[k], tr_laps[k]);
                 fclose(ft);
+            }
+            if (sc_tau > 0.) {
+                if ((rc = iblb_get_scalar(ctx, &sc_win, sc_out.data()))) return die(ctx, rc, "iblb_get_scalar");
+                outfile = raw_data + to_string(it) + "-scalar.dat";
+                FILE* fc = fopen(outfile.c_str(), "w");
+                if (!fc) {
+                    fprintf(stderr, "cannot write %s: %s\n", outfile.c_str(), strerror(errno));
+                    return 1;
+                }
+                for (int j = 0; j < sc_win.ny; j++)
+                    for (int i = 0; i < sc_win.nx; i++)
+                        fprintf(fc, "%d\t%d\t%.17g\n", i * sc_sx, j * sc_sy, sc_out[(size_t)j * sc_win.nx + i]);
+                fclose(fc);
             }
             if (av_stride > 0 && !av_first) {
                 outfile = raw_data + to_string(it) + "-mean.dat";

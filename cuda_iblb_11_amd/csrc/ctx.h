@@ -3,7 +3,8 @@
 //   iblb_ctx.hip   lifecycle, state, Lagrangian points, timing, checkpoint / restart
 //   ctx_read.hip   the readers: the current state to the host in the reference layouts, windowed
 //                  fields and reductions, point sampling, the output gather
-//   ctx_observe.hip  what iblb_step runs between the pieces of a call: passive tracers, averaged fields
+//   ctx_observe.hip  what iblb_step runs between the pieces of a call: passive tracers, averaged fields,
+//                  the passive scalar
 //   ctx_step.hip   halo exchange, the one-step / two-step / deep schedules, iblb_step, local and
 //                  RCCL groups
 //   ctx_band.hip   the IB band cycle (K iterations per cycle with an owed force every iteration)
@@ -206,6 +207,16 @@ struct iblb_ctx {
     int av_nbins = 1, av_planes = 0;
     iblbh::Periodic av_ev;  // count: samples taken since iblb_set_average / iblb_reset_average
     std::vector<long long> av_count;  // samples per bin
+    // passive scalar (iblb_set_scalar).  sc_alloc == nullptr: none.  One allocation: two buffers of five planes
+    // (sc_g, ping-pong; sc_cur holds the post-stream populations) and the two-plane velocity scratch sc_uv, each
+    // plane ncol * L.rows doubles, [x * rows + y].  With a scalar iblb_step stops at the iterations of sc_ev and
+    // does sc_ev.stride substeps there with the velocity of that moment (ctx_observe.hip)
+    double* sc_alloc = nullptr;
+    double* sc_g[2] = {nullptr, nullptr};
+    double* sc_uv = nullptr;
+    int sc_cur = 0;
+    iblb_scalar sc_cfg{};   // as given (stride also in sc_ev)
+    iblbh::Periodic sc_ev;  // count: events run since iblb_set_scalar
     // state machine
     int phase = iblbh::PH_EMPTY;
     long long t = 0;
@@ -416,9 +427,10 @@ int group_refused(iblb_ctx* c, const char* what);
 
 // ---- observers (ctx_observe.hip): run by iblb_step on the context's stream, no host synchronise ----
 long long next_event(const iblb_ctx* c);  // the next iteration at which an observer runs (LLONG_MAX: none set)
-int run_events(iblb_ctx* c);              // every observer due at c->t: the tracers, then the averages
+int run_events(iblb_ctx* c);              // every observer due at c->t: the tracers, the averages, the scalar
 void tracers_free(iblb_ctx* c);
 void average_free(iblb_ctx* c);
+void scalar_free(iblb_ctx* c);
 
 // ---- the read scaffold: what every reader and observer is made of ----
 // f(g, H): the populations and the halo of the current state, typed by the context's precision; the

@@ -1,10 +1,29 @@
 // ctx_observe.hip — the observers of a context (ctx.h): what iblb_step runs between the pieces of a call
-// with the state held fixed.  Passive tracers (iblb_set_tracers) and time- and phase-averaged fields
-// (iblb_set_average), each on a Periodic schedule; iblb_step asks next_event where to cut a call and
-// run_events to run what is due there.  Built from the read scaffold of ctx.h like the readers.
+// with the state held fixed.  Passive tracers (iblb_set_tracers), time- and phase-averaged fields
+// (iblb_set_average) and the passive scalar (iblb_set_scalar), each on a Periodic schedule; iblb_step asks
+// next_event where to cut a call and run_events to run what is due there.  Built from the read scaffold of
+// ctx.h like the readers.
+#include <cmath>
+
 #include "ctx.h"
 
 namespace iblbh {
+
+void scalar_free(iblb_ctx* c) {
+    if (c->sc_alloc) (void)hipFree(c->sc_alloc);
+    c->sc_alloc = c->sc_g[0] = c->sc_g[1] = c->sc_uv = nullptr;
+    c->sc_cur = 0;
+    c->sc_cfg = iblb_scalar{};
+    c->sc_ev.clear();
+}
+
+static ScalarGeom scalar_geom(const iblb_ctx* c) {
+    return ScalarGeom{c->ncol, c->ny, c->L.rows, (long)c->ncol * c->L.rows};
+}
+
+static ScalarRule scalar_rule(const iblb_scalar& k) {
+    return ScalarRule{1.0 / k.tau, {k.wall_kind[0], k.wall_kind[1]}, {k.wall_value[0], k.wall_value[1]}};
+}
 
 void tracers_free(iblb_ctx* c) {
     for (void* p : {(void*)c->tr_x, (void*)c->tr_y, (void*)c->tr_laps})
@@ -61,18 +80,43 @@ static int average_update(iblb_ctx* c) {
     return IBLB_OK;
 }
 
+// One event of the scalar on the context's stream: the state prepared as for a reader (the band streams
+// joined, the owed IB force evaluated), then `stride` substeps with the velocity of this state: the first
+// evaluates it from the fluid populations and leaves it in the scratch, the others read the scratch.
+static int scalar_update(iblb_ctx* c) {
+    if (!single_slab(c))  // the context joined a group after iblb_set_scalar: its lattice is the whole lattice's
+        return fail(c, IBLB_ERR_UNSUPPORTED, "scalar: a lone slab only; remove it before joining a group");
+    int rc = band_join(c);
+    if (rc || (rc = prepare_read(c))) return rc;
+    const FieldsArgs a = point_args(c, IBLB_FIELD_UX | IBLB_FIELD_UY);
+    const ScalarGeom S = scalar_geom(c);
+    const ScalarRule R = scalar_rule(c->sc_cfg);
+    HIP_TRY(c, with_state(c, [&](auto* g, auto H) {
+        return launch_scalar_first(g, c->L, H, a, S, R, c->sc_g[c->sc_cur], c->sc_g[c->sc_cur ^ 1], c->sc_uv, c->stream);
+    }));
+    c->sc_cur ^= 1;
+    for (int k = 1; k < c->sc_ev.stride; ++k) {
+        HIP_TRY(c, launch_scalar_next(S, R, c->sc_g[c->sc_cur], c->sc_g[c->sc_cur ^ 1], c->sc_uv, c->stream));
+        c->sc_cur ^= 1;
+    }
+    c->sc_ev.advance();
+    return IBLB_OK;
+}
+
 long long next_event(const iblb_ctx* c) {
     long long next = LLONG_MAX;
     if (c->tr_n > 0) next = std::min(next, c->tr_ev.next);
     if (c->av_fields) next = std::min(next, c->av_ev.next);
+    if (c->sc_alloc) next = std::min(next, c->sc_ev.next);
     return next;
 }
 
-// Neither observer changes the state: at a common iteration their order is free
+// No observer changes the fluid state: at a common iteration their order is free
 int run_events(iblb_ctx* c) {
     int rc = IBLB_OK;
     if (c->tr_n > 0 && c->t == c->tr_ev.next && (rc = tracer_update(c))) return rc;
-    if (c->av_fields && c->t == c->av_ev.next) rc = average_update(c);
+    if (c->av_fields && c->t == c->av_ev.next && (rc = average_update(c))) return rc;
+    if (c->sc_alloc && c->t == c->sc_ev.next) rc = scalar_update(c);
     return rc;
 }
 
@@ -233,6 +277,97 @@ int iblb_average_info(iblb_ctx* c, iblb_window* w, unsigned* fields, int* stride
     if (nbins) *nbins = c->av_nbins;
     if (flags) *flags = c->av_flags;
     if (samples_total) *samples_total = c->av_ev.count;
+    return IBLB_OK;
+}
+
+// ---- passive scalar -----------------------------------------------------------------------------------
+int iblb_set_scalar(iblb_ctx* c, const iblb_scalar* cfg, const double* c0, const double* g0) {
+    if (!c) return IBLB_ERR_ARG;
+    if (cfg) {
+        if (!std::isfinite(cfg->tau) || !(cfg->tau > 0.5)) return fail(c, IBLB_ERR_ARG, "tau must be finite and > 0.5");
+        if (cfg->stride < 1) return fail(c, IBLB_ERR_ARG, "stride must be >= 1");
+        for (int k = 0; k < 2; ++k) {
+            if (cfg->wall_kind[k] != IBLB_SCALAR_WALL_NOFLUX && cfg->wall_kind[k] != IBLB_SCALAR_WALL_VALUE)
+                return fail(c, IBLB_ERR_ARG, "wall_kind: an unknown IBLB_SCALAR_WALL_* value");
+            if (cfg->wall_kind[k] == IBLB_SCALAR_WALL_VALUE && !std::isfinite(cfg->wall_value[k]))
+                return fail(c, IBLB_ERR_ARG, "wall_value must be finite where the wall kind is IBLB_SCALAR_WALL_VALUE");
+        }
+        if ((c0 != nullptr) == (g0 != nullptr)) return fail(c, IBLB_ERR_ARG, "exactly one of c0 and g0 must be given");
+        if (!single_slab(c))
+            return fail(c, IBLB_ERR_UNSUPPORTED,
+                        "iblb_set_scalar: a lone slab only (the scalar on the slabs of a group is not built)");
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!cfg) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        scalar_free(c);
+        return IBLB_OK;
+    }
+    // the state the equilibrium is taken at (c0), as a reader sees it
+    int rc = band_join(c);
+    if (rc || (rc = prepare_read(c))) return rc;
+    // the new buffers first: a failed allocation leaves the previous scalar as it was
+    const ScalarGeom S = scalar_geom(c);
+    const size_t N = (size_t)c->ncol * c->ny, planes_in = c0 ? 1 : 5;
+    if ((size_t)S.plane > SIZE_MAX / sizeof(double) / 12)
+        return fail(c, IBLB_ERR_NOMEM, "iblb_set_scalar: the populations exceed the address space");
+    DevBuf d, in;
+    HIP_TRY(c, hipMalloc(&d.p, 12 * (size_t)S.plane * sizeof(double)));
+    HIP_TRY(c, hipMalloc(&in.p, planes_in * N * sizeof(double)));
+    double* buf = (double*)d.p;
+    HIP_TRY(c, hipMemsetAsync(buf, 0, 12 * (size_t)S.plane * sizeof(double), c->stream));
+    HIP_TRY(c, hipMemcpyAsync(in.p, c0 ? c0 : g0, planes_in * N * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, launch_scalar_in((const double*)in.p, S, (int)planes_in, buf, c->stream));
+    if (c0) {
+        const FieldsArgs a = point_args(c, IBLB_FIELD_UX | IBLB_FIELD_UY);
+        HIP_TRY(c, with_state(c, [&](auto* g, auto H) { return launch_scalar_init(g, c->L, H, a, S, buf, buf, c->stream); }));
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    scalar_free(c);
+    c->sc_alloc = buf;
+    d.p = nullptr;
+    c->sc_g[0] = buf;
+    c->sc_g[1] = buf + 5 * S.plane;
+    c->sc_uv = buf + 10 * S.plane;
+    c->sc_cur = 0;
+    c->sc_cfg = *cfg;
+    c->sc_ev.stride = cfg->stride;
+    c->sc_ev.arm(c->t);
+    return IBLB_OK;
+}
+
+int iblb_get_scalar(iblb_ctx* c, const iblb_window* w, double* out) {
+    if (!c) return IBLB_ERR_ARG;
+    if (!c->sc_alloc) return fail(c, IBLB_ERR_STATE, "iblb_get_scalar: no scalar is set");
+    iblb_window win;
+    int lo = 0, nxl = 0, rc;
+    if ((rc = window_part(c, w, &win, &lo, &nxl))) return rc;
+    if (!out) return fail(c, IBLB_ERR_ARG, "c is NULL");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t nb = (size_t)win.nx * win.ny * sizeof(double);
+    DevBuf d;
+    HIP_TRY(c, hipMalloc(&d.p, nb));
+    HIP_TRY(c, launch_scalar_out(c->sc_g[c->sc_cur], scalar_geom(c), win.x0, win.y0, win.nx, win.ny, win.sx, win.sy,
+                                 (double*)d.p, c->stream));
+    return read_back(c, out, d.p, nb);
+}
+
+int iblb_get_scalar_populations(iblb_ctx* c, double* g) {
+    if (!c) return IBLB_ERR_ARG;
+    if (!c->sc_alloc) return fail(c, IBLB_ERR_STATE, "iblb_get_scalar_populations: no scalar is set");
+    if (!g) return fail(c, IBLB_ERR_ARG, "g is NULL");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t nb = 5 * (size_t)c->ncol * c->ny * sizeof(double);
+    DevBuf d;
+    HIP_TRY(c, hipMalloc(&d.p, nb));
+    HIP_TRY(c, launch_scalar_populations_out(c->sc_g[c->sc_cur], scalar_geom(c), (double*)d.p, c->stream));
+    return read_back(c, g, d.p, nb);
+}
+
+int iblb_scalar_info(iblb_ctx* c, iblb_scalar* cfg, long long* updates) {
+    if (!c) return IBLB_ERR_ARG;
+    if (cfg) *cfg = c->sc_cfg;
+    if (updates) *updates = c->sc_ev.count;
     return IBLB_OK;
 }
 

@@ -725,7 +725,7 @@ int iblb_step(iblb_ctx* c, int nsteps) {
     int rc = check_ready(c);
     if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    // The observers (ctx_observe.hip: passive tracers, averaged fields) cut the call at their event
+    // The observers (ctx_observe.hip: passive tracers, averaged fields, the passive scalar) cut the call at their event
     // iterations: each piece (at most the smaller stride) is scheduled as a call of its own, then with that
     // state held fixed the observers due there run, as if the caller had stepped the piece, read the fields
     // and done their work on the host.  No observer: no event ahead, and the one piece is the whole call
@@ -733,7 +733,7 @@ int iblb_step(iblb_ctx* c, int nsteps) {
         const long long next = next_event(c);
         const long long to_event = next == LLONG_MAX ? LLONG_MAX : next - c->t;
         if (to_event < 1)
-            return fail(c, IBLB_ERR_STATE, "tracers / averages: the next event iteration is not ahead of the state");
+            return fail(c, IBLB_ERR_STATE, "tracers / averages / scalar: the next event iteration is not ahead of the state");
         const int piece = (int)std::min<long long>(nsteps - done, to_event);
         if ((rc = step_call(c, piece)) || (rc = run_events(c))) return rc;
         done += piece;

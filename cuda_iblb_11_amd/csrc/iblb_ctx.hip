@@ -441,7 +441,7 @@ void iblb_destroy(iblb_ctx* c) {
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     void* bufs[] = {c->g_alloc, c->cil_samples, c->cil_lasts, c->cil_bpoints, c->rho0, c->u0, c->force0, c->d_s,
                     c->d_us, c->d_Fs, c->d_eps, c->d_Fs_sum, c->fd_alloc, c->fl_alloc, c->d_Q, c->red_buf, c->d_sch_s,
-                    c->d_sch_us, c->d_sch_eps, c->tr_x, c->tr_y, c->tr_laps, c->av_buf};
+                    c->d_sch_us, c->d_sch_eps, c->tr_x, c->tr_y, c->tr_laps, c->av_buf, c->sc_alloc};
     for (void* p : bufs)
         if (p) (void)hipFree(p);
     if (c->sig) (void)hipFree(c->sig);
@@ -535,6 +535,7 @@ int iblb_set_state(iblb_ctx* c, const double* rho, const double* u, const double
     c->bnd_w = INT_MAX;
     c->tr_ev.arm(c->t);  // tracers stay; their updates count from the new state
     c->av_ev.arm(c->t);  // so do the averages: sums and counts kept, samples from the new state
+    c->sc_ev.arm(c->t);  // and the scalar: populations and event count kept, the velocity from the new state
     return IBLB_OK;
 }
 
@@ -838,6 +839,7 @@ int iblb_load_checkpoint(iblb_ctx* c, const char* path) {
     c->phase = PH_EMPTY;
     tracers_free(c);  // a checkpoint holds no tracers (the caller saves them with iblb_get_tracers)
     average_free(c);  // nor averages
+    scalar_free(c);   // nor the scalar (the caller saves it with iblb_get_scalar_populations)
     if (iv[CK_CILIA]) {
         iblb_cilia k{(int)iv[CK_CNUM], dv[CK_CSPACE], (int)iv[CK_CT], (int)iv[CK_CPSTEP]};
         if ((rc = iblb_set_cilia(c, &k))) return rc;

@@ -258,6 +258,37 @@ hipError_t launch_average_accum(const T* g, Layout L, Halo<T> H, const FieldsArg
 // The planes of one bin transposed into iblb_get_fields' layout: out[(p*nyw + j)*nxl + il].
 hipError_t launch_average_readout(const double* acc, int nxl, int nyw, int planes, double* out, hipStream_t s);
 
+// Passive scalar (scalar_kernels.hip; include/iblb.h iblb_set_scalar): a D2Q5 lattice of five planes of doubles,
+// s[i * plane + x * rows + y], two such buffers and a two-plane velocity scratch uv in the same order.
+struct ScalarGeom {
+    int ncol, ny;
+    long rows;   // column stride (Layout::rows)
+    long plane;  // plane stride: ncol * rows
+};
+struct ScalarRule {
+    double omega;          // 1.0 / tau
+    int wall_kind[2];      // IBLB_SCALAR_WALL_*: below row 0, above row ny - 1
+    double wall_value[2];
+};
+// One substep src -> dst (distinct buffers).  first: the velocity from the fluid state by cell_state of
+// field_eval.h (of FieldsArgs the window members are unused), also left in uv; next: the velocity read from uv.
+template <typename T>
+hipError_t launch_scalar_first(const T* f, Layout L, Halo<T> H, const FieldsArgs& a, ScalarGeom S, ScalarRule R,
+                               const double* src, double* dst, double* uv, hipStream_t s);
+hipError_t launch_scalar_next(ScalarGeom S, ScalarRule R, const double* src, double* dst, const double* uv,
+                              hipStream_t s);
+// dst's five planes = the equilibrium of C = c[x * rows + y] at the fluid state's velocity; c may be dst's plane 0.
+template <typename T>
+hipError_t launch_scalar_init(const T* f, Layout L, Halo<T> H, const FieldsArgs& a, ScalarGeom S, const double* c,
+                              double* dst, hipStream_t s);
+// `planes` (1 .. 5) planes in the reference layout, ref[p * ncol * ny + y * ncol + x], into dev's planes; the five
+// planes of dev out the same way; C = (((g0+g1)+g2)+g3)+g4 on a window (validated by the caller) into
+// out[j * nxw + i].
+hipError_t launch_scalar_in(const double* ref, ScalarGeom S, int planes, double* dev, hipStream_t s);
+hipError_t launch_scalar_populations_out(const double* dev, ScalarGeom S, double* out, hipStream_t s);
+hipError_t launch_scalar_out(const double* dev, ScalarGeom S, int x0, int y0, int nxw, int nyw, int sx, int sy,
+                             double* out, hipStream_t s);
+
 // q(u^t) of the current state for the flux column (added to *out).
 template <typename T>
 hipError_t launch_flux(const T* g, Layout L, Halo<T> H, const double* fdense, long fplane,

@@ -1,0 +1,205 @@
+// scalar_kernels.hip — the passive scalar (include/iblb.h iblb_set_scalar): a D2Q5 BGK advection-diffusion
+// lattice for one concentration C that iblb_step advances at its event iterations with the fluid velocity of
+// that moment held fixed.
+//
+// Layout.  Five planes of ncol * rows doubles, s[i * plane + x * rows + y] (rows = ny rounded up to whole waves,
+// as the dense force): y fastest, one lane per cell, lanes along y, so every load and store of a wave is one
+// contiguous run.  Two such buffers (ping-pong) and a two-plane scratch for ux, uy in the same order.
+//
+// Substep: PUSH form.  A lane loads the five populations and the velocity of its own cell (7 planes), relaxes,
+// and stores p_i to the cell the direction points at, plane i (5 planes): 96 bytes per cell.  The streaming map
+// with the wall rules is a bijection of (cell, direction): the population that would leave through a wall goes
+// to the same cell's opposite direction instead, whose own source cell does not exist.  Every destination
+// element has exactly one writer: no atomics, no cross-lane steps.  The stores along y land one row up / down:
+// still one contiguous run per wave, shifted by 8 bytes.
+// The first substep of an event evaluates (ux, uy) with cell_state of field_eval.h, so its bits are those of
+// iblb_get_fields, and leaves them in the scratch; the later substeps read the scratch, not the nine populations.
+// Contraction is off everywhere: one rounding per operation, as the rule of include/iblb.h states it.
+//
+// The transposes between the ABI's layouts ([y * nx + x]) and the device's go through an LDS tile so that both
+// sides coalesce.
+#include "field_eval.h"
+
+namespace iblb {
+
+namespace {
+
+constexpr int TILE = 32;  // transposes: TILE x TILE elements per workgroup of TILE x 8 lanes
+constexpr double SW0 = 1.0 / 3.0, SW1 = 1.0 / 6.0;
+
+// One cell of a substep: g[5] of cell (x, y) relaxed towards the equilibrium at (ux, uy) and pushed into dst.
+__device__ __forceinline__ void scalar_push(const double g[5], double ux, double uy, const ScalarGeom& S,
+                                            const ScalarRule& R, int x, int y, double* __restrict__ dst) {
+#pragma clang fp contract(off)
+    const double C = (((g[0] + g[1]) + g[2]) + g[3]) + g[4];
+    const double a[5] = {0.0, ux, -ux, uy, -uy};
+    double p[5];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+        const double geq = ((i == 0 ? SW0 : SW1) * C) * (1.0 + 3.0 * a[i]);
+        p[i] = g[i] - R.omega * (g[i] - geq);
+    }
+    const long o = (long)x * S.rows + y;
+    const long oxp = (long)(x + 1 < S.ncol ? x + 1 : 0) * S.rows + y;
+    const long oxm = (long)(x > 0 ? x - 1 : S.ncol - 1) * S.rows + y;
+    dst[o] = p[0];
+    dst[S.plane + oxp] = p[1];
+    dst[2 * S.plane + oxm] = p[2];
+    if (y + 1 < S.ny) dst[3 * S.plane + o + 1] = p[3];
+    else dst[4 * S.plane + o] = R.wall_kind[1] == IBLB_SCALAR_WALL_VALUE ? (2.0 * SW1) * R.wall_value[1] - p[3] : p[3];
+    if (y > 0) dst[4 * S.plane + o - 1] = p[4];
+    else dst[3 * S.plane + o] = R.wall_kind[0] == IBLB_SCALAR_WALL_VALUE ? (2.0 * SW1) * R.wall_value[0] - p[4] : p[4];
+}
+
+// grid: (ncol, ceil(ny / 256)); one lane per cell
+template <typename T>
+__global__ __launch_bounds__(256) void scalar_first_kernel(const T* __restrict__ f, Layout L, Halo<T> H, FieldsArgs a,
+                                                           ScalarGeom S, ScalarRule R, const double* __restrict__ src,
+                                                           double* __restrict__ dst, double* __restrict__ uv) {
+    const int x = blockIdx.x, y = blockIdx.y * 256 + threadIdx.x;
+    if (x >= S.ncol || y >= S.ny) return;
+    const long o = (long)x * S.rows + y;
+    double g[5], pop[9], r, ux, uy;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) g[i] = src[i * S.plane + o];
+    cell_state<T>(f, L, H, a, x, y, pop, r, ux, uy);
+    uv[o] = ux;
+    uv[S.plane + o] = uy;
+    scalar_push(g, ux, uy, S, R, x, y, dst);
+}
+
+__global__ __launch_bounds__(256) void scalar_next_kernel(ScalarGeom S, ScalarRule R, const double* __restrict__ src,
+                                                          double* __restrict__ dst, const double* __restrict__ uv) {
+    const int x = blockIdx.x, y = blockIdx.y * 256 + threadIdx.x;
+    if (x >= S.ncol || y >= S.ny) return;
+    const long o = (long)x * S.rows + y;
+    double g[5];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) g[i] = src[i * S.plane + o];
+    scalar_push(g, uv[o], uv[S.plane + o], S, R, x, y, dst);
+}
+
+// The equilibrium of C = c[x * rows + y] (device layout: plane 0 of dst's own transposed input) at the cell's
+// velocity, into the five planes of dst; c may be plane 0 of dst (a lane reads its element before it writes it)
+template <typename T>
+__global__ __launch_bounds__(256) void scalar_init_kernel(const T* __restrict__ f, Layout L, Halo<T> H, FieldsArgs a,
+                                                          ScalarGeom S, const double* c, double* dst) {
+#pragma clang fp contract(off)
+    const int x = blockIdx.x, y = blockIdx.y * 256 + threadIdx.x;
+    if (x >= S.ncol || y >= S.ny) return;
+    const long o = (long)x * S.rows + y;
+    double pop[9], r, ux, uy;
+    cell_state<T>(f, L, H, a, x, y, pop, r, ux, uy);
+    const double C = c[o];
+    const double av[5] = {0.0, ux, -ux, uy, -uy};
+#pragma unroll
+    for (int i = 0; i < 5; ++i) dst[i * S.plane + o] = ((i == 0 ? SW0 : SW1) * C) * (1.0 + 3.0 * av[i]);
+}
+
+// dev[p * plane + x * rows + y] = ref[p * ncol * ny + y * ncol + x] for the planes p < gridDim.z
+__global__ __launch_bounds__(TILE * 8) void scalar_in_kernel(const double* __restrict__ ref, ScalarGeom S,
+                                                             double* __restrict__ dev) {
+    __shared__ double tile[TILE][TILE + 1];
+    const double* src = ref + blockIdx.z * ((long)S.ncol * S.ny);
+    double* dst = dev + blockIdx.z * S.plane;
+    const int y0 = blockIdx.x * TILE, x0 = blockIdx.y * TILE;
+    for (int r = threadIdx.y; r < TILE; r += 8) {  // rows of the tile along y, lanes along x
+        const int y = y0 + r, x = x0 + threadIdx.x;
+        if (x < S.ncol && y < S.ny) tile[r][threadIdx.x] = src[(long)y * S.ncol + x];
+    }
+    __syncthreads();
+    for (int r = threadIdx.y; r < TILE; r += 8) {  // rows of the tile along x, lanes along y
+        const int x = x0 + r, y = y0 + threadIdx.x;
+        if (x < S.ncol && y < S.ny) dst[(long)x * S.rows + y] = tile[threadIdx.x][r];
+    }
+}
+
+// SUM false: out[p * nxw * nyw + j * nxw + i] = dev[p * plane + X * rows + Y] for the planes p < gridDim.z;
+// SUM true:  out[j * nxw + i] = (((g0 + g1) + g2) + g3) + g4 of cell (X, Y);  X = x0 + i sx, Y = y0 + j sy
+template <bool SUM>
+__global__ __launch_bounds__(TILE * 8) void scalar_out_kernel(const double* __restrict__ dev, ScalarGeom S, int x0,
+                                                              int y0, int nxw, int nyw, int sx, int sy,
+                                                              double* __restrict__ out) {
+#pragma clang fp contract(off)
+    __shared__ double tile[TILE][TILE + 1];
+    const double* src = dev + (SUM ? 0 : blockIdx.z * S.plane);
+    double* dst = out + (SUM ? 0 : blockIdx.z * ((long)nxw * nyw));
+    const int j0 = blockIdx.x * TILE, i0 = blockIdx.y * TILE;
+    for (int r = threadIdx.y; r < TILE; r += 8) {  // rows of the tile along i, lanes along j
+        const int i = i0 + r, j = j0 + threadIdx.x;
+        if (i < nxw && j < nyw) {
+            // the host validated the window; the cell is clamped all the same (as the field kernels do)
+            const int x = min(max(x0 + i * sx, 0), S.ncol - 1), y = min(max(y0 + j * sy, 0), S.ny - 1);
+            const double* q = src + (long)x * S.rows + y;
+            tile[r][threadIdx.x] = SUM ? (((q[0] + q[S.plane]) + q[2 * S.plane]) + q[3 * S.plane]) + q[4 * S.plane] : q[0];
+        }
+    }
+    __syncthreads();
+    for (int r = threadIdx.y; r < TILE; r += 8) {  // rows of the tile along j, lanes along i
+        const int j = j0 + r, i = i0 + threadIdx.x;
+        if (i < nxw && j < nyw) dst[(long)j * nxw + i] = tile[threadIdx.x][r];
+    }
+}
+
+inline bool geom_ok(const ScalarGeom& S) {
+    return S.ncol > 0 && S.ny > 0 && S.rows >= S.ny && S.plane >= (long)S.ncol * S.rows;
+}
+inline dim3 cell_grid(const ScalarGeom& S) { return dim3((unsigned)S.ncol, (unsigned)((S.ny + 255) / 256)); }
+inline dim3 tile_grid(int nx, int ny, int planes) {
+    return dim3((unsigned)((ny + TILE - 1) / TILE), (unsigned)((nx + TILE - 1) / TILE), (unsigned)planes);
+}
+
+}  // namespace
+
+template <typename T>
+hipError_t launch_scalar_first(const T* f, Layout L, Halo<T> H, const FieldsArgs& a, ScalarGeom S, ScalarRule R,
+                               const double* src, double* dst, double* uv, hipStream_t s) {
+    if (!geom_ok(S) || S.ncol != L.ncol || S.ny != L.ny) return hipErrorInvalidValue;
+    scalar_first_kernel<T><<<cell_grid(S), 256, 0, s>>>(f, L, H, a, S, R, src, dst, uv);
+    return hipGetLastError();
+}
+
+hipError_t launch_scalar_next(ScalarGeom S, ScalarRule R, const double* src, double* dst, const double* uv,
+                              hipStream_t s) {
+    if (!geom_ok(S)) return hipErrorInvalidValue;
+    scalar_next_kernel<<<cell_grid(S), 256, 0, s>>>(S, R, src, dst, uv);
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t launch_scalar_init(const T* f, Layout L, Halo<T> H, const FieldsArgs& a, ScalarGeom S, const double* c,
+                              double* dst, hipStream_t s) {
+    if (!geom_ok(S) || S.ncol != L.ncol || S.ny != L.ny) return hipErrorInvalidValue;
+    scalar_init_kernel<T><<<cell_grid(S), 256, 0, s>>>(f, L, H, a, S, c, dst);
+    return hipGetLastError();
+}
+
+hipError_t launch_scalar_in(const double* ref, ScalarGeom S, int planes, double* dev, hipStream_t s) {
+    if (!geom_ok(S) || planes < 1 || planes > 5) return hipErrorInvalidValue;
+    scalar_in_kernel<<<tile_grid(S.ncol, S.ny, planes), dim3(TILE, 8), 0, s>>>(ref, S, dev);
+    return hipGetLastError();
+}
+
+hipError_t launch_scalar_populations_out(const double* dev, ScalarGeom S, double* out, hipStream_t s) {
+    if (!geom_ok(S)) return hipErrorInvalidValue;
+    scalar_out_kernel<false><<<tile_grid(S.ncol, S.ny, 5), dim3(TILE, 8), 0, s>>>(dev, S, 0, 0, S.ncol, S.ny, 1, 1, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_scalar_out(const double* dev, ScalarGeom S, int x0, int y0, int nxw, int nyw, int sx, int sy,
+                             double* out, hipStream_t s) {
+    if (!geom_ok(S) || nxw < 1 || nyw < 1) return hipErrorInvalidValue;
+    scalar_out_kernel<true><<<tile_grid(nxw, nyw, 1), dim3(TILE, 8), 0, s>>>(dev, S, x0, y0, nxw, nyw, sx, sy, out);
+    return hipGetLastError();
+}
+
+template hipError_t launch_scalar_first<double>(const double*, Layout, Halo<double>, const FieldsArgs&, ScalarGeom,
+                                                ScalarRule, const double*, double*, double*, hipStream_t);
+template hipError_t launch_scalar_first<float>(const float*, Layout, Halo<float>, const FieldsArgs&, ScalarGeom,
+                                               ScalarRule, const double*, double*, double*, hipStream_t);
+template hipError_t launch_scalar_init<double>(const double*, Layout, Halo<double>, const FieldsArgs&, ScalarGeom,
+                                               const double*, double*, hipStream_t);
+template hipError_t launch_scalar_init<float>(const float*, Layout, Halo<float>, const FieldsArgs&, ScalarGeom,
+                                              const double*, double*, hipStream_t);
+
+}  // namespace iblb

@@ -445,6 +445,54 @@ class Lattice:
         with np.errstate(invalid="ignore", divide="ignore"):
             return {m: v / float(a["samples"]) for m, v in a["sum"].items()}
 
+    # -- passive scalar ---------------------------------------------------------------------------
+    def set_scalar(self, c0=None, g0=None, tau: float = 1.0, stride: int = 1,
+                   walls=((L.SCALAR_WALL_NOFLUX, 0.0), (L.SCALAR_WALL_NOFLUX, 0.0))) -> None:
+        """A concentration field that `step` advects with the fluid and diffuses on the device, D = (tau - 0.5)/3:
+        `stride` substeps every `stride` iterations with the velocity of that moment (iblb_set_scalar).  c0:
+        (ny, nx) concentrations, set to equilibrium at the current velocity; or g0: (5, ny, nx) populations as
+        `scalar_populations` returns them (a restart).  walls: ((kind, value) below row 0, (kind, value) above
+        the top row), kind L.SCALAR_WALL_NOFLUX or L.SCALAR_WALL_VALUE.  A lone slab only."""
+        def arr(a, n):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.size != n:
+                raise ValueError(f"expected {n} values, got {a.size}")
+            return a
+        c0, g0 = arr(c0, self.N), arr(g0, 5 * self.N)
+        (k0, v0), (k1, v1) = walls
+        cfg = L.Scalar(float(tau), int(stride), (C.c_int * 2)(int(k0), int(k1)),
+                       (C.c_double * 2)(0.0 if v0 is None else float(v0), 0.0 if v1 is None else float(v1)))
+        self._check(self._lib.iblb_set_scalar(self._h, C.byref(cfg), _ptr(c0), _ptr(g0)))
+
+    def remove_scalar(self) -> None:
+        """Remove the scalar: `step` is then exactly what it is without one."""
+        self._check(self._lib.iblb_set_scalar(self._h, None, None, None))
+
+    def scalar_info(self) -> dict:
+        """{"tau", "stride", "walls": ((kind, value), (kind, value)), "updates"} of the scalar
+        (iblb_scalar_info); stride == 0: none set."""
+        cfg, n = L.Scalar(), C.c_longlong(0)
+        self._check(self._lib.iblb_scalar_info(self._h, C.byref(cfg), C.byref(n)))
+        return {"tau": cfg.tau, "stride": cfg.stride,
+                "walls": tuple((cfg.wall_kind[k], cfg.wall_value[k]) for k in range(2)), "updates": n.value}
+
+    def scalar(self, window=None) -> np.ndarray:
+        """C on a strided window, (ny, nx) of the window (iblb_get_scalar); None: the whole lattice."""
+        w = _window(window)
+        shape = (self.ny, self.nx) if w is None else (max(w.ny, 0), max(w.nx, 0))
+        out = np.empty(shape)
+        self._check(self._lib.iblb_get_scalar(self._h, None if w is None else C.byref(w), _ptr(out)))
+        return out
+
+    def scalar_populations(self) -> np.ndarray:
+        """The five post-stream populations, (5, ny, nx) (iblb_get_scalar_populations): what `set_scalar(g0=...)`
+        takes."""
+        g = np.empty((5, self.ny, self.x_count))
+        self._check(self._lib.iblb_get_scalar_populations(self._h, _ptr(g)))
+        return g
+
     @property
     def steps(self) -> int:
         n = C.c_longlong(0)

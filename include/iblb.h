@@ -412,6 +412,59 @@ int iblb_get_average(iblb_ctx* ctx, int bin, double* sum, double* sum_sq, double
 int iblb_average_info(iblb_ctx* ctx, iblb_window* w, unsigned* fields, int* stride, int* nbins, unsigned* flags,
                       long long* samples_total);
 
+/* Passive scalar: one concentration field C that the context itself advects with the fluid and diffuses while
+ * iblb_step runs, so that transport and mixing (a solute cleared by the cilia, uptake at a wall) need neither a
+ * readback of u per iteration nor a solver on the host.  A D2Q5 BGK advection-diffusion lattice: five populations
+ * g_i per cell, stored in double whatever the context's precision; a lone slab only. */
+#define IBLB_SCALAR_WALL_NOFLUX 0   /* halfway bounce-back: no flux through the wall      */
+#define IBLB_SCALAR_WALL_VALUE  1   /* halfway anti-bounce-back: C = wall_value at the wall */
+typedef struct iblb_scalar {
+    double tau;            /* relaxation time, finite and > 0.5; diffusivity D = (tau - 0.5)/3 */
+    int    stride;         /* >= 1: an event every `stride` iterations, `stride` substeps per event */
+    int    wall_kind[2];   /* [0]: wall below row 0, [1]: wall above row YDIM-1 */
+    double wall_value[2];  /* used (and required finite) where the kind is _VALUE */
+} iblb_scalar;
+/* iblb_set_scalar.  c0 is [N] in the reference layout (j = y*XDIM + x); g0 is [5N], plane-major g0[i*N + j], the
+ * post-stream populations.  Exactly one of c0 and g0 must be non-NULL: with c0 the populations are the equilibrium
+ * geq_i below at the ux, uy that iblb_get_fields returns at the call; g0 is taken as it is (a restart).  The call
+ * records t0 = iblb_get_step and replaces any previous scalar; cfg == NULL (c0 and g0 ignored) removes the scalar,
+ * and iblb_step is then exactly what it is without it.  tau not finite or <= 0.5, stride < 1, a wall kind other than
+ * the two above, a non-finite wall value under _VALUE, both or neither of c0 and g0: IBLB_ERR_ARG, checked before
+ * anything is touched.  A slab of a local or RCCL group: IBLB_ERR_UNSUPPORTED.  The new buffers are allocated
+ * before the old ones are freed: any error, IBLB_ERR_NOMEM included, leaves the previous scalar as it was.
+ * Update rule.  Directions i = 0..4 with c_i = (0,0), (+1,0), (-1,0), (0,+1), (0,-1); weights w0 = 1.0/3.0,
+ * w1..4 = 1.0/6.0; omega = 1.0/tau, computed on the host in double.  An event runs after each of the iterations
+ * t0 + stride, t0 + 2 stride, ...: it takes ux, uy of every cell as iblb_get_fields returns them at that moment,
+ * bit for bit (in every phase, an owed IB force included), holds them fixed and does `stride` substeps, every
+ * operation in double with one rounding and no contraction.  One substep, per cell:
+ *   C     = (((g0 + g1) + g2) + g3) + g4
+ *   a     = (0, ux, -ux, uy, -uy)
+ *   geq_i = (w_i*C) * (1.0 + 3.0*a_i)
+ *   p_i   = g_i - omega*(g_i - geq_i)
+ *   g_i'(x, y) = p_i(x - c_ix, y - c_iy)                                  periodic in x
+ *   g_3'(x, 0) = p_4(x, 0)                   no-flux wall below row 0;    _VALUE: (2.0*w1)*wall_value[0] - p_4(x, 0)
+ *   g_4'(x, YDIM-1) = p_3(x, YDIM-1)         no-flux wall above the top;  _VALUE: (2.0*w1)*wall_value[1] - p_3(x, YDIM-1)
+ * Nothing is filtered: a non-finite value spreads.  The scheme conserves sum(C) between no-flux walls, and diffuses
+ * with D = (tau - 0.5)/3 (its error grows towards tau = 0.5 and with the cell Peclet number |u|/D).
+ * iblb_step(nsteps) with a scalar cuts the call at the union of the scalar's, the tracers' and the averages' event
+ * sets; at a common iteration all due observers run, and since none changes the fluid state their order is free.  A
+ * stride >= K (IBLB_SWEEP_DEPTH) keeps the deep sweep between events; stride 1 costs the one-step path at every
+ * iteration.  A substep is one launch on the context's stream, one lane per cell, 96 bytes per cell, without a host
+ * synchronise.
+ * iblb_get_scalar returns C = (((g0+g1)+g2)+g3)+g4 of the stored populations on the window into c[j*w.nx + i]
+ * (the window rules of iblb_get_fields; NULL = the whole lattice).  No scalar set: IBLB_ERR_STATE; a bad window or
+ * c == NULL: IBLB_ERR_ARG, no output touched.  iblb_get_scalar_populations returns g [5N] in the layout of g0.
+ * iblb_scalar_info returns the configuration and the events run since the set (either pointer may be NULL);
+ * cfg->stride == 0: no scalar is set.
+ * iblb_set_state keeps the scalar (populations and event count) and re-bases t0 to the new state's step count 0.
+ * Checkpoints do not hold the scalar: iblb_load_checkpoint removes it; the caller saves it with
+ * iblb_get_scalar_populations and restores it through g0.  A context that joins a group after the set fails its
+ * next event with IBLB_ERR_UNSUPPORTED.  iblb_destroy frees the scalar. */
+int iblb_set_scalar(iblb_ctx* ctx, const iblb_scalar* cfg, const double* c0, const double* g0);
+int iblb_get_scalar(iblb_ctx* ctx, const iblb_window* w, double* c);
+int iblb_get_scalar_populations(iblb_ctx* ctx, double* g);
+int iblb_scalar_info(iblb_ctx* ctx, iblb_scalar* cfg, long long* updates);
+
 /* Timing: when enabled (1) every collide-stream launch is bracketed by HIP events on the
  * stream it runs on; iblb_get_timing() returns the sums (and resets them if reset).  enabled = 2:
  * only the deep (K-iteration) launches are timed, by their own dispatch / completion signals (no
