@@ -10,6 +10,8 @@
 //   ctx_band.hip   the IB band cycle (K iterations per cycle with an owed force every iteration)
 // Every reader and observer is built from the read scaffold below (with_state ... read_back).
 //   band_plan.h    the band cycle's planner: pure host functions (no HIP), checked on the CPU
+//   deep_plan.h    the deep sweep's launch planner (builds, sweeps, edge waves, a call's depths,
+//                  IBLB_DEEP_BUILD): pure host functions too, applied by lbm_sweep_impl.h's launchers
 //
 // Time-step bookkeeping.  The reference iteration (main.cu:852-909) is
 //   f0,F = equilibrium(u^t, rho^t, force^t); f1 = collision(f^t); f^{t+1} = stream(f1);

@@ -522,7 +522,7 @@ static int deep_slab_step(iblb_ctx* c, int K) {
 // A device wait (deep_slab_step, band_step) that timed out leaves wrong populations behind: the call
 // that ran it fails (the flag is read after the compute stream is synchronised).  With profiling on,
 // the two-way handshake's done word is also checked against the edge-wave count the launcher
-// computed on the host (launch_sweepk_mode's edge_waves): every interior has ended here.
+// computed on the host (deep_plan.h:deep_edge_waves): every interior has ended here.
 int check_wait_err(iblb_ctx* c) {
     if (!c->sig_err) return IBLB_OK;
     if (__atomic_load_n(c->sig_err, __ATOMIC_ACQUIRE) != 0) {
@@ -634,18 +634,6 @@ using namespace iblbh;
 
 extern "C" {
 
-// Depth of the next deep launch without IB, r >= K-1 iterations left in the call: K, or K-1 where
-// launches of K-1 (j of them) leave a multiple of K, so that r = j (K-1) + m K needs no two-iteration
-// or one-step remainder (every r >= (K-1)(K-2) qualifies: 20 = 4 x 5 at K = 6, 500 = 4 x 5 + 80 x 6).
-// A remainder costs more than the depth: M f64 20 iterations at K = 6 as 3 x 6 + 2 took 0.111 ms per
-// iteration against 0.097 as 4 x 5 (profiles/r04/depth).
-static int deep_depth(const iblb_ctx* c, int r) {
-    const int K = c->sweep_depth;
-    if (K < 4) return K;
-    const int j = (K - r % K) % K;
-    return (j > 0 && (long)j * (K - 1) <= r) ? K - 1 : K;
-}
-
 // nsteps iterations by the fastest applicable schedule per iteration (band cycles, deep sweeps,
 // two-iteration sweeps, one-step iterations); the band streams may still run at the end
 static int step_range(iblb_ctx* c, int nsteps) {
@@ -675,7 +663,7 @@ static int step_range(iblb_ctx* c, int nsteps) {
             continue;
         }
         if ((rc = band_join(c))) return rc;
-        const int d = nsteps - s >= K - 1 ? deep_depth(c, nsteps - s) : K;
+        const int d = nsteps - s >= K - 1 ? deep_depth(K, nsteps - s) : K;
         if (d >= 3 && nsteps - s >= d && sweep_ready(c)) {
             if (single_slab(c)) {
                 if ((rc = is_f64(c) ? sweepk_step<double>(c, d) : sweepk_step<float>(c, d))) return rc;

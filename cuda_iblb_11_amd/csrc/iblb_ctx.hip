@@ -227,24 +227,6 @@ static int check_slab_points(iblb_ctx* c, size_t np, const float* s) {
     return IBLB_OK;
 }
 
-// IBLB_DEEP_BUILD: a comma list of split, pack, window, or the one word plain (no feature)
-static bool parse_deep_build(const char* e, DeepBuild* out) {
-    const std::string v(e);
-    DeepBuild b{false, false, false};
-    if (v != "plain")
-        for (size_t i = 0; i <= v.size();) {
-            const size_t j = std::min(v.find(',', i), v.size());
-            const std::string w = v.substr(i, j - i);
-            if (w == "split") b.split = true;
-            else if (w == "pack") b.pack = true;
-            else if (w == "window") b.window = true;
-            else return false;
-            i = j + 1;
-        }
-    *out = b;
-    return true;
-}
-
 }  // namespace iblbh
 
 using namespace iblbh;

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "deep_plan.h"
 #include "iblb_device.h"
 #include "skip_box.h"
 
@@ -90,13 +91,7 @@ struct FusedArgs {
 // Two iterations per launch (lbm_sweep.hip): g^t -> g^{t+2}, no IB force owed in between.
 // (SkipBox, MAX_SKIP: skip_box.h)
 
-// The deep sweep's build features (lbm_sweep_impl.h:launch_sweepk_vs picks the kernel build from them;
-// one that does not apply to a (type, cells per lane, layout) combination is ignored)
-struct DeepBuild {
-    bool split;   // the wall-row chunks as their own sweep family (one cell per lane), the inner chunks preshifted
-    bool pack;    // f32, two cells per lane: both cells' collides as one packed f32x2 computation
-    bool window;  // two cells per lane, split: the moving populations wait in an LDS window
-};
+// (DeepBuild, the deep sweep's build features: deep_plan.h)
 
 template <typename T>
 struct Sweep2Args {
@@ -147,7 +142,7 @@ struct Sweep2Args {
 // columns of the buffer itself (a group slab's boundary sweeps after the halo exchange)
 template <typename T>
 hipError_t launch_sweep2(Sweep2Args<T> a, bool ghost, hipStream_t s);
-// K = depth (3 .. 6) iterations per launch: g^t -> g^{t+K}; ghost as above (a
+// K = depth (3 .. 7) iterations per launch: g^t -> g^{t+K}; ghost as above (a
 // boundary sweep of output columns [0, K) reads columns -K .. 2K-1).  col_step 0: balanced widths.
 // start / stop: recorded by the kernel's dispatch / completion signals (no marker packets)
 template <typename T>
@@ -160,7 +155,7 @@ hipError_t launch_seq_signal(unsigned* p, unsigned v, hipStream_t s);
 // until it is non-zero or `ticks` of the device wall clock have passed, so that the work queued
 // behind it on `s` starts late, as behind a neighbour rank that reaches its exchange late.
 hipError_t launch_test_hold(const unsigned* word, unsigned long long ticks, hipStream_t s);
-// Resident waves per CU of a deep-sweep configuration; *nch = its row chunks for ny rows.
+// Resident waves per CU of a deep-sweep configuration's plain build; *nch = its row chunks for ny rows.
 template <typename T>
 int sweepk_geometry(int depth, int vs, bool ghost, int ny, int* nch);
 

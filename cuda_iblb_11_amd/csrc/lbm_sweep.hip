@@ -2,45 +2,31 @@
 // sweeps (built per depth in lbm_sweepk<K>.hip); the kernels' code is in lbm_sweep_impl.h.
 #include "lbm_sweep_impl.h"
 
-namespace iblb {
-
 // the K-iteration kernels are built in lbm_sweepk<K>.hip
-#define IBLB_SWEEPK_EXTERN(T, K, S)                                                          \
-    extern template hipError_t launch_sweepk_depth<T, K, S>(const Sweep2Args<T>&, hipStream_t, hipEvent_t, hipEvent_t); \
-    extern template int deep_geometry<T, K, S>(int, int, int*);
-#define IBLB_SWEEPK_EXTERN_K(K)                                                                               \
-    IBLB_SWEEPK_EXTERN(double, K, false) IBLB_SWEEPK_EXTERN(double, K, true) IBLB_SWEEPK_EXTERN(float, K, false) \
-    IBLB_SWEEPK_EXTERN(float, K, true)
-IBLB_SWEEPK_EXTERN_K(3)
-IBLB_SWEEPK_EXTERN_K(4)
-IBLB_SWEEPK_EXTERN_K(5)
-IBLB_SWEEPK_EXTERN_K(6)
-IBLB_SWEEPK_EXTERN_K(7)
+IBLB_SWEEPK_EXTERN(3)
+IBLB_SWEEPK_EXTERN(4)
+IBLB_SWEEPK_EXTERN(5)
+IBLB_SWEEPK_EXTERN(6)
+IBLB_SWEEPK_EXTERN(7)
+
+namespace iblb {
 
 template <typename T, bool SLAB>
 static hipError_t launch_sweepk_slab(const Sweep2Args<T>& a, int depth, hipStream_t s, hipEvent_t stop,
                                      hipEvent_t start) {
-    if (depth == 3) return launch_sweepk_depth<T, 3, SLAB>(a, s, stop, start);
-    if (depth == 4) return launch_sweepk_depth<T, 4, SLAB>(a, s, stop, start);
-    if (depth == 5) return launch_sweepk_depth<T, 5, SLAB>(a, s, stop, start);
-    if (depth == 6) return launch_sweepk_depth<T, 6, SLAB>(a, s, stop, start);
-    if (depth == 7) return launch_sweepk_depth<T, 7, SLAB>(a, s, stop, start);
-    return hipErrorInvalidValue;
+    return with_depth(depth, hipErrorInvalidValue,
+                      [&](auto k) { return launch_sweepk_depth<T, decltype(k)::value, SLAB>(a, s, stop, start); });
 }
-
 
 template <typename T>
 int sweepk_geometry(int depth, int vs, bool slab, int ny, int* nch) {
     *nch = 0;
     if (vs != 1 && vs != 2) return 0;
-    switch (depth) {
-        case 3: return slab ? deep_geometry<T, 3, true>(vs, ny, nch) : deep_geometry<T, 3, false>(vs, ny, nch);
-        case 4: return slab ? deep_geometry<T, 4, true>(vs, ny, nch) : deep_geometry<T, 4, false>(vs, ny, nch);
-        case 5: return slab ? deep_geometry<T, 5, true>(vs, ny, nch) : deep_geometry<T, 5, false>(vs, ny, nch);
-        case 6: return slab ? deep_geometry<T, 6, true>(vs, ny, nch) : deep_geometry<T, 6, false>(vs, ny, nch);
-        case 7: return slab ? deep_geometry<T, 7, true>(vs, ny, nch) : deep_geometry<T, 7, false>(vs, ny, nch);
-        default: return 0;
-    }
+    return with_depth(depth, 0, [&](auto k) {
+        constexpr int K = decltype(k)::value;
+        *nch = deep_nch(K, vs, ny);
+        return slab ? deep_waves_per_cu<T, K, true>(vs) : deep_waves_per_cu<T, K, false>(vs);
+    });
 }
 template int sweepk_geometry<double>(int, int, bool, int, int*);
 template int sweepk_geometry<float>(int, int, bool, int, int*);

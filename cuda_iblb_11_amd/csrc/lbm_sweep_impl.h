@@ -1,6 +1,8 @@
 // lbm_sweep_impl.h — the temporally blocked kernels (templates), shared by lbm_sweep.hip (two
-// iterations per launch, dispatch, halo packing) and lbm_sweepk{3,4,5,6}.hip (the K-iteration
-// kernels of one depth each: separate translation units build in parallel).
+// iterations per launch, dispatch, halo packing) and lbm_sweepk{3,4,5,6,7}.hip (the K-iteration
+// kernels of one depth each: separate translation units build in parallel).  The host decisions of a
+// deep launch (which build, how many sweeps, waves and edge waves) are deep_plan.h's; the launchers
+// at the end of this file apply them.
 //
 // Two reference iterations per launch (temporal blocking along x).
 //
@@ -32,15 +34,15 @@
 #include <hip/hip_ext.h>
 
 #include <climits>
+#include <type_traits>
+#include <utility>
 
+#include "deep_plan.h"
 #include "lbm_vec.h"
 
 namespace iblb {
 
-// sweep only (MODE bits 1, 2 as in lbm_vec.h): no software prefetch of the next column (two-step
-// sweeps); the deep sweep's wall split (sweepk_kernel)
-enum { MODE_NO_PREFETCH = 8, MODE_SPLIT = 16, MODE_PACK = 64, MODE_SKIP = 128, MODE_PRESHIFT = 256, MODE_LDSWIN = 512,
-       MODE_WT_STORE = 1024 };
+// (the sweeps' MODE bits beyond lbm_vec.h's: deep_plan.h)
 
 namespace {
 
@@ -359,7 +361,7 @@ hipError_t launch_sweep2(Sweep2Args<T> a, bool slab, hipStream_t s) {
     return hipErrorInvalidValue;
 }
 
-// ---- K iterations per launch (lone slab, K = 3 .. 6) ------------------------------------------
+// ---- K iterations per launch (lone slab and group slab, K = 3 .. 7) ---------------------------
 // sweepk_kernel: g^t -> g^{t+K}, the walk keeping K-1 register windows (g^{t+1} .. g^{t+K-1}).
 // Same wave geometry, order and walking directions as sweep2_kernel.  Valid rows shrink by one
 // per level at the wave's edges (the +-1-row pulls of the end lanes take garbage from level 2
@@ -1264,64 +1266,18 @@ static long resident_waves(int cus) {
     return waves_per_cu<T, VS, MODE, K, SLAB, WPE>() * (cus > 0 ? std::min(cus, ncu) : ncu);
 }
 
-// wall split: sweeps of a wall chunk per sweep of an inner chunk, in quarters.  With one-cell wall
-// walks (no spills) the launch time is the inner waves' whatever the ratio: M f32 0.319-0.322 ms per
-// launch for 0.5 ... 1.5 (profiles/r03s1); the first split (two-cell wall walks with spills) needed 2
-// (0.305-0.320 ms, profiles/r03sp, r03r2).
-constexpr int WALL_SWEEPS_X4 = 4;
-
+// One build's launch: sweeps and waves sized by deep_plan.h from this build's resident waves
 template <typename T, int VS, int MODE, int K, bool SLAB, int WPE>
 static hipError_t launch_sweepk_mode(Sweep2Args<T> b, hipStream_t s, hipEvent_t stop, hipEvent_t start) {
-    long waves;
-    if (b.col_step <= 0) {
-        // balanced sweeps: the wave count a whole number of device-wide rounds (the waves of one
-        // launch all do the same work, so a partial last round idles the chip), sweeps close to
-        // the requested W columns
-        const long n = b.col_end - b.col_begin;
-        const long slots = resident_waves<T, VS, MODE, K, SLAB, WPE>(b.cus);
-        long ns = (n + b.W - 1) / b.W;
-        if (MODE & MODE_SPLIT) {
-            // wall split: nin inner chunks with ns sweeps, the two wall chunks with ns * r sweeps each
-            const long nin = b.wall_ch0, r4 = VS == 1 ? 6 : WALL_SWEEPS_X4;  // VS 1: wall walks ~1.4x the inner
-            if (slots > 0) {
-                const long rounds = std::max(1L, (ns * (4 * nin + 2 * r4) / 4 + slots / 2) / slots);
-                ns = std::max(1L, 4 * rounds * slots / (4 * nin + 2 * r4));
-            }
-            b.nsweep = (int)std::min(ns, n);
-            b.nsweep_w = (int)std::min((ns * r4 + 3) / 4, n);
-            waves = (long)b.nsweep * nin + 2L * b.nsweep_w;
-        } else {
-            if (slots > 0) {
-                const long rounds = std::max(1L, (ns * b.nch + slots / 2) / slots);
-                ns = std::max(1L, rounds * slots / b.nch);
-            }
-            b.nsweep = (int)std::min(ns, n);
-            waves = (long)b.nsweep * b.nch;
-        }
-    } else if (MODE & MODE_SPLIT) {  // fixed sweeps (a slab's boundary sweeps): the wall chunks too
-        b.nsweep_w = b.nsweep;
-        waves = (long)b.nsweep * b.wall_ch0 + 2L * b.nsweep_w;
-    } else {
-        waves = (long)b.nsweep * b.nch;
-    }
-    if (b.edge_waves) {  // the waves that will add to done_cnt (sweepk_kernel's `edge`)
-        auto edges = [&](int nsw) {
-            int e = 0;
-            for (int sw = 0; sw < nsw; ++sw) {
-                int xa, xb;
-                if (b.col_step > 0) {
-                    xa = b.col_begin + sw * b.col_step;
-                    xb = std::min(xa + b.W, b.col_end);
-                } else {
-                    balanced_range(b.col_begin, b.col_end, sw, nsw, xa, xb);
-                }
-                e += (xa < b.wait_lo || xb > b.wait_hi) ? 1 : 0;
-            }
-            return e;
-        };
-        *b.edge_waves = (MODE & MODE_SPLIT) ? edges(b.nsweep) * b.wall_ch0 + 2 * edges(b.nsweep_w)
-                                            : edges(b.nsweep) * b.nch;
-    }
+    constexpr bool SPLIT = (MODE & MODE_SPLIT) != 0;
+    const long slots = b.col_step <= 0 ? resident_waves<T, VS, MODE, K, SLAB, WPE>(b.cus) : 0;
+    const DeepSweeps p =
+        deep_sweeps(SPLIT, VS, b.col_begin, b.col_end, b.col_step, b.W, b.nsweep, b.nch, b.wall_ch0, slots);
+    b.nsweep = p.nsweep;
+    b.nsweep_w = p.nsweep_w;
+    if (b.edge_waves)  // the waves that will add to done_cnt (sweepk_kernel's `edge`)
+        *b.edge_waves = deep_edge_waves(SPLIT, b.col_begin, b.col_end, b.col_step, b.W, b.nsweep, b.nsweep_w, b.nch,
+                                        b.wall_ch0, b.wait_lo, b.wait_hi);
     if (b.kinfo) {  // which build ran (iblb_timing: the bench line's limiter names it)
         static int vgprs = -1;
         if (vgprs < 0) {
@@ -1336,7 +1292,7 @@ static hipError_t launch_sweepk_mode(Sweep2Args<T> b, hipStream_t s, hipEvent_t 
         b.kinfo[2] = (int)(waves_per_cu<T, VS, MODE, K, SLAB, WPE>() / 4);
         b.kinfo[3] = vgprs;
     }
-    const unsigned blocks = (unsigned)((waves + 3) / 4);
+    const unsigned blocks = (unsigned)((p.waves + 3) / 4);
     if (stop || start)  // the events ride on the kernel's own signals: no marker packets around it
         hipExtLaunchKernelGGL(sweepk_kernel<T, VS, MODE, K, SLAB, WPE>, dim3(blocks), dim3(256), 0, s, start, stop, 0, b);
     else
@@ -1344,57 +1300,30 @@ static hipError_t launch_sweepk_mode(Sweep2Args<T> b, hipStream_t s, hipEvent_t 
     return hipGetLastError();
 }
 
-// The build of one (type, cells per lane, depth, layout) for the features asked (DeepBuild); a feature
-// that does not apply here is ignored.  MODE bit 0 (nontemporal stores) is in every build.
+// The build (mode, wpe) of deep_builds' list: walking the list is what instantiates the kernels, so
+// no build exists that the list does not name.  A choice outside the list is an error.
+template <typename T, int VS, int K, bool SLAB, size_t... I>
+static hipError_t launch_sweepk_build(int mode, int wpe, const Sweep2Args<T>& b, hipStream_t s, hipEvent_t stop,
+                                      hipEvent_t start, std::index_sequence<I...>) {
+    constexpr DeepBuilds L = deep_builds(sizeof(T) == 4, VS, SLAB);
+    hipError_t e = hipErrorInvalidValue;
+    (void)((mode == L.k[I].mode && wpe == L.k[I].wpe &&
+            ((e = launch_sweepk_mode<T, VS, L.k[I].mode, K, SLAB, L.k[I].wpe>(b, s, stop, start)), true)) ||
+           ...);
+    return e;
+}
+
+// The build of one (type, cells per lane, depth, layout) for the features asked (deep_choose)
 template <typename T, int VS, int K, bool SLAB>
 static hipError_t launch_sweepk_vs(const Sweep2Args<T>& a, hipStream_t s, hipEvent_t stop, hipEvent_t start) {
-    constexpr int G = ghost_lanes<K, VS>();
-    const int rows_per_wave = (64 - 2 * G) * VS;  // owned rows
     constexpr bool F32 = sizeof(T) == 4;
+    const DeepChoice c = deep_choose(F32, VS, SLAB, K, a.L.ny, a.nskip, a.build);
     Sweep2Args<T> b = a;
-    b.nch = (a.L.ny + rows_per_wave - 1) / rows_per_wave;
-    // The wall split: two cells per lane in the inner chunks, and f32 with one (a group slab).  Rows:
-    // [0, OWN1) bottom wall chunk, inner chunks of rows_per_wave, top wall chunk from an even row (two-cell
-    // lanes of the inner chunks never straddle it) holding the last OWN1 or fewer rows
-    if constexpr (VS == 2 || F32) {
-        constexpr int OWN1 = 64 - 2 * ghost_lanes<K, 1>();
-        const int top = (a.L.ny - OWN1 + 1) & ~1;
-        // f32, one cell per lane (a group slab's band cycle): the split with the skip regions too
-        constexpr bool SPLIT_SKIP = F32 && VS == 1 && !SLAB;
-        if (a.build.split && (a.nskip == 0 || SPLIT_SKIP) && top > OWN1) {
-            b.wall_top = top;
-            b.wall_ch0 = (top - OWN1 + rows_per_wave - 1) / rows_per_wave;
-            if constexpr (SPLIT_SKIP)  // three waves per SIMD (four: 6 dwords of scratch spills)
-                if (a.nskip > 0)
-                    return launch_sweepk_mode<T, VS, 1 | MODE_SPLIT | MODE_PRESHIFT | MODE_SKIP, K, SLAB, 3>(b, s, stop, start);
-            if constexpr (F32 && VS == 2)
-                if (a.build.pack) {
-                    // the window (round 5): two of the three moving populations in LDS, three waves per SIMD
-                    if constexpr (!SLAB)
-                        if (a.build.window)
-                            return launch_sweepk_mode<T, VS, 1 | MODE_SPLIT | MODE_PACK | MODE_LDSWIN, K, SLAB, 3>(b, s, stop,
-                                                                                                         start);
-                    // the inner chunks packed, two waves per SIMD (the packed inner walk needs 191 VGPRs; forced
-                    // to three waves it spills 21 dwords: 0.417 vs 0.323 ms per M f32 launch, profiles/r04/pack)
-                    return launch_sweepk_mode<T, VS, 1 | MODE_SPLIT | MODE_PACK, K, SLAB, 2>(b, s, stop, start);
-                }
-            // waves per SIMD: f32 three at two cells per lane, four at one; f64 one
-            constexpr int WPE = F32 ? (VS == 2 ? 3 : 4) : 1;
-            if constexpr (!F32)  // (VS == 2) the LDS window of the inner chunks
-                if (a.build.window)
-                    return launch_sweepk_mode<T, VS, 1 | MODE_SPLIT | MODE_PRESHIFT | MODE_LDSWIN, K, SLAB, WPE>(b, s, stop,
-                                                                                                           start);
-            return launch_sweepk_mode<T, VS, 1 | MODE_SPLIT | MODE_PRESHIFT, K, SLAB, WPE>(b, s, stop, start);
-        }
-    }
-    // the IB band cycle's deep and boundary sweeps beside its last level: patch output rows left out
-    if (a.nskip > 0) return launch_sweepk_mode<T, VS, 1 | MODE_SKIP, K, SLAB, 1>(b, s, stop, start);
-    if constexpr (F32 && VS == 2)
-        if (a.build.pack) return launch_sweepk_mode<T, VS, 1 | MODE_PACK, K, SLAB, 1>(b, s, stop, start);
-    // (the preshift in every chunk, without the split, is slower than this plain walk: M f64 0.559 vs 0.521 ms
-    // per launch, profiles/r04/split64: the wall waves, which set the launch time, wait on the wall rows'
-    // uniform loads; with the split the inner chunks take it and the wall waves have slack)
-    return launch_sweepk_mode<T, VS, 1, K, SLAB, 1>(b, s, stop, start);
+    b.nch = c.nch;
+    b.wall_top = c.wall_top;
+    b.wall_ch0 = c.wall_ch0;
+    return launch_sweepk_build<T, VS, K, SLAB>(c.mode, c.wpe, b, s, stop, start,
+                                               std::make_index_sequence<deep_builds(F32, VS, SLAB).n>{});
 }
 
 // cells per lane: 2 or 1 (4 in f32 measured slower: one wave per SIMD, profiles/r01d4_*)
@@ -1405,17 +1334,41 @@ hipError_t launch_sweepk_depth(const Sweep2Args<T>& a, hipStream_t s, hipEvent_t
     return hipErrorInvalidValue;
 }
 
-
-// resident waves per CU and waves per launch column-chunk geometry of one configuration (the
-// context sizes the CUs it reserves for the boundary sweeps with it)
+// Resident waves per CU of one configuration (the context sizes the CUs it reserves for the boundary
+// sweeps with it): those of the plain build (MODE 1, one wave per SIMD), although the slabs run the
+// split builds (785 / 273).  Sizing the reservation from the build that runs would change the
+// context's reserved CUs: a change of behaviour, left for its own measurement.
 template <typename T, int K, bool SLAB>
-int deep_geometry(int vs, int ny, int* nch) {
-    if (vs == 2) {
-        *nch = (ny + (64 - 2 * ghost_lanes<K, 2>()) * 2 - 1) / ((64 - 2 * ghost_lanes<K, 2>()) * 2);
-        return (int)waves_per_cu<T, 2, 1, K, SLAB, 1>();
-    }
-    *nch = (ny + (64 - 2 * ghost_lanes<K, 1>()) - 1) / (64 - 2 * ghost_lanes<K, 1>());
-    return (int)waves_per_cu<T, 1, 1, K, SLAB, 1>();
+int deep_waves_per_cu(int vs) {
+    return (int)(vs == 2 ? waves_per_cu<T, 2, 1, K, SLAB, 1>() : waves_per_cu<T, 1, 1, K, SLAB, 1>());
 }
+
+// f(std::integral_constant<int, K>) for depth = K in 3 .. 7 (the depths that are built), else `none`
+template <typename R, typename F>
+static R with_depth(int depth, R none, F f) {
+    switch (depth) {
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 5: return f(std::integral_constant<int, 5>{});
+        case 6: return f(std::integral_constant<int, 6>{});
+        case 7: return f(std::integral_constant<int, 7>{});
+        default: return none;
+    }
+}
+
+// lbm_sweepk<K>.hip: the launchers (and through them the kernels) of depth K; lbm_sweep.hip declares
+// them extern
+#define IBLB_SWEEPK_INST(PREFIX, T, K, S)                                                                            \
+    PREFIX template hipError_t launch_sweepk_depth<T, K, S>(const Sweep2Args<T>&, hipStream_t, hipEvent_t, hipEvent_t); \
+    PREFIX template int deep_waves_per_cu<T, K, S>(int);
+#define IBLB_SWEEPK_UNIT_(PREFIX, K)                                                                               \
+    namespace iblb {                                                                                                \
+    IBLB_SWEEPK_INST(PREFIX, double, K, false)                                                                      \
+    IBLB_SWEEPK_INST(PREFIX, double, K, true)                                                                       \
+    IBLB_SWEEPK_INST(PREFIX, float, K, false)                                                                       \
+    IBLB_SWEEPK_INST(PREFIX, float, K, true)                                                                        \
+    }
+#define IBLB_SWEEPK_UNIT(K) IBLB_SWEEPK_UNIT_(, K)
+#define IBLB_SWEEPK_EXTERN(K) IBLB_SWEEPK_UNIT_(extern, K)
 
 }  // namespace iblb

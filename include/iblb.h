@@ -161,7 +161,7 @@ typedef struct iblb_timing {
     long long band_par_cycles;  /* of those, run with the last level beside the deep sweep (lone slab) */
     /* deep launches (lone slab, slab interiors, band cycles) and the iterations they advanced, counted
      * whether or not profiling events are on: a call of n iterations mixes depths K and K-1 so that
-     * no two-iteration or one-step remainder is left where n allows it (ctx_step.hip:deep_depth) */
+     * no two-iteration or one-step remainder is left where n allows it (deep_plan.h:deep_depth) */
     long long deep_launches;
     long long deep_iterations;
     /* launches of an RCCL group slab whose waves waited on a device word instead of a queue wait
