@@ -82,10 +82,14 @@ class Window(C.Structure):
     _fields_ = [("x0", C.c_int), ("y0", C.c_int), ("nx", C.c_int), ("ny", C.c_int), ("sx", C.c_int), ("sy", C.c_int)]
 
 
-# IBLB_FIELD_* bits of iblb_get_fields, in ascending bit order (the order of the output planes)
+# the fluid's IBLB_FIELD_* bits of iblb_get_fields, in ascending bit order (the order of the output planes)
 FIELDS = {"rho": 1, "ux": 2, "uy": 4, "vort": 8, "sxx": 16, "sxy": 32, "syy": 64}
-# what iblb_reduce_fields accepts: the fields and the reduce-only IBLB_QTY_* bits, in ascending bit order
-QUANTITIES = {**FIELDS, "momx": 128, "momy": 256, "ke": 512, "usq": 1024}
+# the passive scalar's fields (IBLB_FIELD_C, _CUX, _CUY): every reader takes them once a scalar is set
+SCALAR_FIELDS = {"c": 4096, "cux": 8192, "cuy": 16384}
+# what iblb_get_fields, iblb_sample_points and iblb_set_average accept, in ascending bit order
+READ_FIELDS = {**FIELDS, **SCALAR_FIELDS}
+# what iblb_reduce_fields accepts: those and the reduce-only IBLB_QTY_* bits, in ascending bit order
+QUANTITIES = {**FIELDS, "momx": 128, "momy": 256, "ke": 512, "usq": 1024, **SCALAR_FIELDS}
 # flags of iblb_set_average
 AVG_SQ = 1
 AVG_UXUY = 2
@@ -160,6 +164,7 @@ _SIGS = {
     "iblb_get_scalar": ([_vp, C.POINTER(Window), _vp], C.c_int),
     "iblb_get_scalar_populations": ([_vp, _vp], C.c_int),
     "iblb_scalar_info": ([_vp, C.POINTER(Scalar), C.POINTER(C.c_longlong)], C.c_int),
+    "iblb_get_scalar_wall_flux": ([_vp, _vp, _vp], C.c_int),
     "iblb_set_profiling": ([_vp, C.c_int], C.c_int),
     "iblb_get_timing": ([_vp, C.POINTER(Timing), C.c_int], C.c_int),
     "iblb_get_timing_ex": ([_vp, C.POINTER(Timing), C.c_ulong, C.c_int], C.c_int),

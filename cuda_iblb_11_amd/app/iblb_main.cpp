@@ -39,7 +39,9 @@
 // D = (tau - 0.5)/3, `stride` substeps every `stride` iterations, default 1) seeded C = 1 for y < YDIM/2 and 0 above,
 // no flux through the walls, and writes <it>-scalar.dat beside the fluid files at every output iteration (BigData or
 // not): one line  x  y  c  per sample of every sx-th column and sy-th row (default 1), lattice units, %.17g.
-// Checkpoints hold no scalar: a restarted run seeds it again.
+// Checkpoints hold no scalar: a restarted run seeds it again.  With IBLB_STATS=1 as well, one more iblb_reduce_fields
+// call (IBLB_FIELD_C, _CUX, _CUY over the whole lattice) appends one line per output iteration to <..>-cstats.dat beside
+// the flux file (lattice units, %.17g):  it  sum(C)  sum(C^2)  min C  max C  sum(C u_x)  sum(C u_y)
 #include <sys/stat.h>
 #include <sys/time.h>
 #include <unistd.h>
@@ -399,6 +401,7 @@ int main(int argc, char* argv[]) {
                              to_string(c_space) + "_" + to_string_3(Re) + "_" + to_string_3(T_num) + "x" +
                              to_string_3(T_pow) + "-flux.dat";
     const std::string stats_path = flux.substr(0, flux.size() - strlen("-flux.dat")) + "-stats.dat";
+    const std::string cstats_path = flux.substr(0, flux.size() - strlen("-flux.dat")) + "-cstats.dat";
     const std::string parameters = raw_data + "/SimLog.txt";
 
     ofstream fsA, fsB, fsC;
@@ -411,6 +414,10 @@ int main(int argc, char* argv[]) {
             fsB.close();
             if (stats_on) {
                 fsB.open(stats_path.c_str(), ofstream::trunc);
+                fsB.close();
+            }
+            if (stats_on && sc_tau > 0.) {
+                fsB.open(cstats_path.c_str(), ofstream::trunc);
                 fsB.close();
             }
         }
@@ -548,6 +555,19 @@ int main(int argc, char* argv[]) {
                 fprintf(fs, "%u\t%.17g\t%.17g\t%.17g\t%.17g\t%.17g\t%d\t%d\t%.17g\t%lld\n", it, st[0].sum, st[1].sum,
                         st[2].sum, st[3].sum, st[4].max, st[4].max_i, st[4].max_j, sqrt(st[4].max) / 0.57735,
                         st[0].nonfinite);
+                fclose(fs);
+            }
+            if (stats_on && sc_tau > 0.) {
+                iblb_field_stats st[3];  // ascending bit order: c, cux, cuy
+                if ((rc = iblb_reduce_fields(ctx, nullptr, IBLB_FIELD_C | IBLB_FIELD_CUX | IBLB_FIELD_CUY, st, nullptr, nullptr)))
+                    return die(ctx, rc, "iblb_reduce_fields");
+                FILE* fs = fopen(cstats_path.c_str(), "a");
+                if (!fs) {
+                    fprintf(stderr, "cannot append to %s: %s\n", cstats_path.c_str(), strerror(errno));
+                    return 1;
+                }
+                fprintf(fs, "%u\t%.17g\t%.17g\t%.17g\t%.17g\t%.17g\t%.17g\n", it, st[0].sum, st[0].sum_sq, st[0].min,
+                        st[0].max, st[1].sum, st[2].sum);
                 fclose(fs);
             }
             if (tr_n > 0) {

@@ -22,8 +22,9 @@ namespace {
 constexpr int TILE = 32;  // read-out: TILE x TILE elements per workgroup of TILE x 8 lanes
 
 // HEAVY: vorticity or a stress component is requested (bits 3 .. 6); the light build carries none of
-// their code.
-template <typename T, bool HEAVY>
+// their code.  SCALAR: one of the scalar's fields is requested (FIELD_SCALAR_BITS): five more loads per sample,
+// one contiguous run per wave each like the fluid's nine; the builds without carry none of that code.
+template <typename T, bool HEAVY, bool SCALAR>
 __global__ __launch_bounds__(256) void average_accum_kernel(const T* __restrict__ g, Layout L, Halo<T> H, FieldsArgs a,
                                                             unsigned flags, double* __restrict__ acc) {
 #pragma clang fp contract(off)
@@ -36,8 +37,8 @@ __global__ __launch_bounds__(256) void average_accum_kernel(const T* __restrict_
     const int xc = min(max(a.xl0 + il * a.sx, 0), L.ncol - 1), y = min(max(a.y0 + j * a.sy, 0), L.ny - 1);
     double f[9], v[7];
 #pragma unroll
-    for (int k = 3; k < 7; ++k) v[k] = 0.;
-    cell_state<T>(g, L, H, a, xc, y, f, v[0], v[1], v[2]);
+    for (int k = SCALAR ? 0 : 3; k < 7; ++k) v[k] = 0.;
+    if (wants_fluid<SCALAR>(a)) cell_state<T>(g, L, H, a, xc, y, f, v[0], v[1], v[2]);
     const double ux = v[1], uy = v[2];
     if constexpr (HEAVY) {
         if (a.fields & IBLB_FIELD_VORT) v[3] = cell_vorticity<T>(g, L, H, a, xc, y, ux);
@@ -57,6 +58,20 @@ __global__ __launch_bounds__(256) void average_accum_kernel(const T* __restrict_
             *q = *q + v[k] * v[k];
         }
         p += n;
+    }
+    if constexpr (SCALAR) {
+        const double c = cell_scalar(a, xc, y);
+        const double vs[3] = {c, c * ux, c * uy};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            if (!((a.fields >> (FIELD_SCALAR_BIT0 + k)) & 1u)) continue;
+            *p = *p + vs[k];
+            if (sq) {
+                double* q = p + (long)nf * n;
+                *q = *q + vs[k] * vs[k];
+            }
+            p += n;
+        }
     }
     if (flags & IBLB_AVG_UXUY) {
         double* q = acc + (long)(sq ? 2 * nf : nf) * n + idx;
@@ -91,10 +106,13 @@ hipError_t launch_average_accum(const T* g, Layout L, Halo<T> H, const FieldsArg
     const long n = (long)a.nxl * a.nyw;
     if (n <= 0) return hipErrorInvalidValue;
     const unsigned grid = (unsigned)((n + 255) / 256);
-    if (a.fields & (IBLB_FIELD_VORT | IBLB_FIELD_SXX | IBLB_FIELD_SXY | IBLB_FIELD_SYY))
-        average_accum_kernel<T, true><<<grid, 256, 0, s>>>(g, L, H, a, flags, acc);
-    else
-        average_accum_kernel<T, false><<<grid, 256, 0, s>>>(g, L, H, a, flags, acc);
+    const bool heavy = a.fields & (IBLB_FIELD_VORT | IBLB_FIELD_SXX | IBLB_FIELD_SXY | IBLB_FIELD_SYY);
+    const bool scalar = a.fields & FIELD_SCALAR_BITS;
+    if (scalar && !a.sc) return hipErrorInvalidValue;
+    if (heavy && scalar) average_accum_kernel<T, true, true><<<grid, 256, 0, s>>>(g, L, H, a, flags, acc);
+    else if (heavy) average_accum_kernel<T, true, false><<<grid, 256, 0, s>>>(g, L, H, a, flags, acc);
+    else if (scalar) average_accum_kernel<T, false, true><<<grid, 256, 0, s>>>(g, L, H, a, flags, acc);
+    else average_accum_kernel<T, false, false><<<grid, 256, 0, s>>>(g, L, H, a, flags, acc);
     return hipGetLastError();
 }
 

@@ -429,7 +429,7 @@ int group_refused(iblb_ctx* c, const char* what);
 
 // ---- observers (ctx_observe.hip): run by iblb_step on the context's stream, no host synchronise ----
 long long next_event(const iblb_ctx* c);  // the next iteration at which an observer runs (LLONG_MAX: none set)
-int run_events(iblb_ctx* c);              // every observer due at c->t: the tracers, the averages, the scalar
+int run_events(iblb_ctx* c);              // every observer due at c->t: the scalar, then the tracers and the averages
 void tracers_free(iblb_ctx* c);
 void average_free(iblb_ctx* c);
 void scalar_free(iblb_ctx* c);
@@ -450,8 +450,11 @@ constexpr unsigned IBLB_FIELD_ALL = IBLB_FIELD_RHO | IBLB_FIELD_UX | IBLB_FIELD_
                                     IBLB_FIELD_SXY | IBLB_FIELD_SYY;
 constexpr unsigned IBLB_QTY_ALL = IBLB_QTY_MOMX | IBLB_QTY_MOMY | IBLB_QTY_KE | IBLB_QTY_USQ;
 
-// at least one bit and none outside `known`: IBLB_FIELD_ALL, or with IBLB_QTY_ALL what iblb_reduce_fields takes
-inline int check_fields(iblb_ctx* c, unsigned fields, unsigned known = IBLB_FIELD_ALL) {
+constexpr unsigned IBLB_FIELD_SCALAR = IBLB_FIELD_C | IBLB_FIELD_CUX | IBLB_FIELD_CUY;  // FIELD_SCALAR_BITS
+
+// at least one bit and none outside `known`: the fields every reader takes, or with IBLB_QTY_ALL what
+// iblb_reduce_fields takes
+inline int check_fields(iblb_ctx* c, unsigned fields, unsigned known = IBLB_FIELD_ALL | IBLB_FIELD_SCALAR) {
     if (fields != 0 && !(fields & ~known)) return IBLB_OK;
     return fail(c, IBLB_ERR_ARG, known & IBLB_QTY_ALL ? "fields: no quantity or an unknown IBLB_FIELD_* / IBLB_QTY_* bit"
                                                       : "fields: no field or an unknown IBLB_FIELD_* bit");
@@ -462,6 +465,15 @@ inline int check_vorticity(iblb_ctx* c, unsigned fields) {
     return fail(c, IBLB_ERR_UNSUPPORTED,
                 "vorticity needs the neighbour slabs' velocity and force: a lone slab only (compute it from "
                 "the gathered u)");
+}
+
+// A scalar's field needs a scalar, which only a lone slab can hold.  Comes after every argument check and
+// check_vorticity, before anything collective.
+inline int check_scalar_fields(iblb_ctx* c, unsigned fields) {
+    if (!(fields & IBLB_FIELD_SCALAR) || (c->sc_alloc && single_slab(c))) return IBLB_OK;
+    return fail(c, IBLB_ERR_STATE,
+                single_slab(c) ? "IBLB_FIELD_C / _CUX / _CUY: no scalar is set (iblb_set_scalar)"
+                               : "IBLB_FIELD_C / _CUX / _CUY: a slab of a group holds no scalar");
 }
 
 // n values summed over the slabs of an RCCL group, on the context's stream; a lone slab: nothing

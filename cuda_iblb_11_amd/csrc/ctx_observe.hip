@@ -67,7 +67,9 @@ static int tracer_update(iblb_ctx* c) {
 static int average_update(iblb_ctx* c) {
     if (!single_slab(c))  // the context joined a group after iblb_set_average: its window is the whole lattice's
         return fail(c, IBLB_ERR_UNSUPPORTED, "averaging: a lone slab only; remove it before joining a group");
-    int rc = band_join(c);
+    int rc = check_scalar_fields(c, c->av_fields);  // (iblb_set_scalar keeps the scalar under such an average)
+    if (rc) return rc;
+    rc = band_join(c);
     if (rc || (rc = prepare_read(c))) return rc;
     const int bin = (int)(c->av_ev.count % c->av_nbins);
     const FieldsArgs a = window_args(c, c->av_win, 0, c->av_win.nx, c->av_fields);
@@ -111,12 +113,13 @@ long long next_event(const iblb_ctx* c) {
     return next;
 }
 
-// No observer changes the fluid state: at a common iteration their order is free
+// No observer changes the fluid state, but an average may sample the scalar: the scalar's event runs first, so
+// that a sample at a common iteration sees C after that iteration's event (include/iblb.h)
 int run_events(iblb_ctx* c) {
     int rc = IBLB_OK;
+    if (c->sc_alloc && c->t == c->sc_ev.next && (rc = scalar_update(c))) return rc;
     if (c->tr_n > 0 && c->t == c->tr_ev.next && (rc = tracer_update(c))) return rc;
-    if (c->av_fields && c->t == c->av_ev.next && (rc = average_update(c))) return rc;
-    if (c->sc_alloc && c->t == c->sc_ev.next) rc = scalar_update(c);
+    if (c->av_fields && c->t == c->av_ev.next) rc = average_update(c);
     return rc;
 }
 
@@ -199,6 +202,7 @@ int iblb_set_average(iblb_ctx* c, const iblb_window* w, unsigned fields, int str
     if (!single_slab(c))
         return fail(c, IBLB_ERR_UNSUPPORTED,
                     "iblb_set_average: a lone slab only (averaging on the slabs of a group is not built)");
+    if (!remove && (rc = check_scalar_fields(c, fields))) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (remove) {
@@ -297,6 +301,9 @@ int iblb_set_scalar(iblb_ctx* c, const iblb_scalar* cfg, const double* c0, const
             return fail(c, IBLB_ERR_UNSUPPORTED,
                         "iblb_set_scalar: a lone slab only (the scalar on the slabs of a group is not built)");
     }
+    if (!cfg && (c->av_fields & IBLB_FIELD_SCALAR))
+        return fail(c, IBLB_ERR_STATE,
+                    "iblb_set_scalar: the current average samples the scalar; remove or replace the average first");
     HIP_TRY(c, hipSetDevice(c->device));
     if (!cfg) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -362,6 +369,18 @@ int iblb_get_scalar_populations(iblb_ctx* c, double* g) {
     HIP_TRY(c, hipMalloc(&d.p, nb));
     HIP_TRY(c, launch_scalar_populations_out(c->sc_g[c->sc_cur], scalar_geom(c), (double*)d.p, c->stream));
     return read_back(c, g, d.p, nb);
+}
+
+int iblb_get_scalar_wall_flux(iblb_ctx* c, double* bottom, double* top) {
+    if (!c) return IBLB_ERR_ARG;
+    if (!c->sc_alloc) return fail(c, IBLB_ERR_STATE, "iblb_get_scalar_wall_flux: no scalar is set");
+    if (!bottom && !top) return fail(c, IBLB_ERR_ARG, "bottom and top are both NULL");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t nb = (size_t)c->ncol * sizeof(double);
+    DevBuf d;
+    HIP_TRY(c, hipMalloc(&d.p, 2 * nb));
+    HIP_TRY(c, launch_scalar_wall_flux(c->sc_g[c->sc_cur], scalar_geom(c), scalar_rule(c->sc_cfg), (double*)d.p, c->stream));
+    return read_back(c, {{bottom, d.p, nb}, {top, (double*)d.p + c->ncol, nb}});
 }
 
 int iblb_scalar_info(iblb_ctx* c, iblb_scalar* cfg, long long* updates) {

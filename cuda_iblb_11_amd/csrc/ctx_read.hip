@@ -61,6 +61,11 @@ FieldsArgs window_args(iblb_ctx* c, const iblb_window& win, int lo, int nxl, uns
     } else {
         a.fdense = ib_force(c);
     }
+    if (fields & IBLB_FIELD_SCALAR) {  // (the callers checked that a scalar is set: check_scalar_fields)
+        a.sc = c->sc_g[c->sc_cur];
+        a.sc_rows = c->L.rows;
+        a.sc_plane = (long)c->ncol * c->L.rows;
+    }
     return a;
 }
 
@@ -197,7 +202,7 @@ int iblb_get_fields(iblb_ctx* c, const iblb_window* w, unsigned fields, double* 
     int lo = 0, nxl = 0;
     if ((rc = window_part(c, w, &win, &lo, &nxl))) return rc;
     if (nxl > 0 && !out) return fail(c, IBLB_ERR_ARG, "out is NULL");
-    if ((rc = check_vorticity(c, fields)) || (rc = prepare_read(c))) return rc;
+    if ((rc = check_vorticity(c, fields)) || (rc = check_scalar_fields(c, fields)) || (rc = prepare_read(c))) return rc;
     if (nxl == 0) return IBLB_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     const int nf = __builtin_popcount(fields);
@@ -213,13 +218,13 @@ int iblb_get_fields(iblb_ctx* c, const iblb_window* w, unsigned fields, double* 
 int iblb_reduce_fields(iblb_ctx* c, const iblb_window* w, unsigned fields, iblb_field_stats* stats, double* row_sum,
                        double* col_sum) {
     if (!c) return IBLB_ERR_ARG;
-    int rc = check_fields(c, fields, IBLB_FIELD_ALL | IBLB_QTY_ALL);
+    int rc = check_fields(c, fields, IBLB_FIELD_ALL | IBLB_QTY_ALL | IBLB_FIELD_SCALAR);
     if (rc) return rc;
     iblb_window win;
     int lo = 0, nxl = 0;
     if ((rc = window_part(c, w, &win, &lo, &nxl))) return rc;
     if (!stats) return fail(c, IBLB_ERR_ARG, "stats is NULL");
-    if ((rc = check_vorticity(c, fields)) || (rc = prepare_read(c))) return rc;
+    if ((rc = check_vorticity(c, fields)) || (rc = check_scalar_fields(c, fields)) || (rc = prepare_read(c))) return rc;
     const int nf = __builtin_popcount(fields);
     if (nxl == 0) {  // none of the window's columns is this slab's
         for (int k = 0; k < nf; ++k)
@@ -268,7 +273,7 @@ int iblb_sample_points(iblb_ctx* c, int n, const double* x, const double* y, uns
     int rc = check_fields(c, fields);
     if (rc) return rc;
     if (!single_slab(c)) return group_refused(c, "iblb_sample_points");
-    if ((rc = check_positions(c, n, x, y))) return rc;
+    if ((rc = check_positions(c, n, x, y)) || (rc = check_scalar_fields(c, fields))) return rc;
     if (n == 0) return IBLB_OK;
     if ((rc = prepare_read(c))) return rc;
     HIP_TRY(c, hipSetDevice(c->device));

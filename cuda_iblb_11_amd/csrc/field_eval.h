@@ -1,6 +1,7 @@
-// field_eval.h — the per-sample evaluation shared by the windowed readers: iblb_get_fields
-// (field_kernels.hip) and iblb_reduce_fields (reduce_kernels.hip) call the same device functions, so
-// a sample has the same bits whether it is copied out or reduced on the device.  Contraction is off
+// field_eval.h — the per-sample evaluation shared by the readers: iblb_get_fields (field_kernels.hip),
+// iblb_reduce_fields (reduce_kernels.hip), iblb_sample_points (tracer_kernels.hip) and iblb_set_average
+// (average_kernels.hip) call the same device functions, so a sample has the same bits whether it is copied
+// out, reduced, interpolated or accumulated on the device.  Contraction is off
 // in every function: one rounding per operation.
 #pragma once
 
@@ -41,6 +42,26 @@ __device__ __forceinline__ void cell_state(const T* __restrict__ g, const Layout
     const double Fy = (a.fdense ? a.fdense[a.fplane + o] : 0.) + a.gy;
     ux = (mx + 0.5 * Fx) / r;
     uy = (my + 0.5 * Fy) / r;
+}
+
+static_assert(FIELD_SCALAR_BITS == (IBLB_FIELD_C | IBLB_FIELD_CUX | IBLB_FIELD_CUY) &&
+                  IBLB_FIELD_C == 1u << FIELD_SCALAR_BIT0 && IBLB_FIELD_CUX == 2u << FIELD_SCALAR_BIT0 &&
+                  IBLB_FIELD_CUY == 4u << FIELD_SCALAR_BIT0,
+              "FIELD_SCALAR_BITS mirrors include/iblb.h");
+
+// A reader's kernel with the scalar's fields needs the fluid state of a cell unless IBLB_FIELD_C is all it was
+// asked for (uniform over the launch); the builds without the scalar always do.
+template <bool SCALAR>
+__device__ __forceinline__ bool wants_fluid(const FieldsArgs& a) {
+    return !SCALAR || (a.fields & ~(unsigned)IBLB_FIELD_C) != 0;
+}
+
+// C of cell (xc, y) exactly as iblb_get_scalar returns it (scalar_out_kernel of scalar_kernels.hip): the five
+// stored populations summed in this order.  Lanes along y: each of the five loads is one contiguous run per wave.
+__device__ __forceinline__ double cell_scalar(const FieldsArgs& a, int xc, int y) {
+#pragma clang fp contract(off)
+    const double* q = a.sc + (long)xc * a.sc_rows + y;
+    return (((q[0] + q[a.sc_plane]) + q[2 * a.sc_plane]) + q[3 * a.sc_plane]) + q[4 * a.sc_plane];
 }
 
 // d(uy)/dx - d(ux)/dy at cell (xc, y) whose own u_x is ux: central differences at lattice spacing 1,

@@ -193,7 +193,15 @@ struct FieldsArgs {
     const double* rho0;       // boot phase: rho^0 / u^0 (slab layout, plane stride fplane) instead of the
     const double* u0;         // moments, and the populations read in place (nullptr: run phase)
     double kvisc;             // -(1 - 1/(2 TAU)): stress = kvisc * PiNeq
+    // the passive scalar's current populations (nullptr unless `fields` holds one of FIELD_SCALAR_BITS), five planes
+    // sc[i * sc_plane + x * sc_rows + y] as ScalarGeom below
+    const double* sc;
+    long sc_rows, sc_plane;
 };
+// IBLB_FIELD_C | IBLB_FIELD_CUX | IBLB_FIELD_CUY: the fields that read the passive scalar.  Every reader kernel has
+// a build with them and one without (a compile-time switch chosen at launch, like HEAVY).
+constexpr unsigned FIELD_SCALAR_BITS = 4096u | 8192u | 16384u;
+constexpr int FIELD_SCALAR_BIT0 = 12;  // the bit number of IBLB_FIELD_C; _CUX and _CUY follow
 // Vorticity (IBLB_FIELD_VORT) wraps the neighbour columns modulo ncol: a lone slab only.
 template <typename T>
 hipError_t launch_fields_out(const T* g, Layout L, Halo<T> H, const FieldsArgs& a, double* out, hipStream_t s);
@@ -201,7 +209,8 @@ hipError_t launch_fields_out(const T* g, Layout L, Halo<T> H, const FieldsArgs& 
 // Window reduction (reduce_kernels.hip; include/iblb.h iblb_reduce_fields): statistics, row sums and
 // column sums of the quantities in a.fields (the IBLB_FIELD_* and IBLB_QTY_* bits) over the samples of
 // FieldsArgs, each evaluated once by the device functions of field_eval.h.
-constexpr int REDUCE_NQ = 11;      // quantities: bit k of `fields`, k < 11
+constexpr int REDUCE_NQ = 11;      // quantities of the fluid: bit k of `fields`, k < 11; bit 11 is none, and the
+                                   // scalar's three (bits 12 .. 14) follow as quantities 11 .. 13 in the builds with them
 constexpr int REDUCE_RS = 10;      // doubles of one statistics record: count, nonfinite, sum, sum_sq, min, max,
                                    // min_i, min_j, max_i, max_j (integers below 2^53: exact)
 constexpr int REDUCE_ROWS = 256;   // window rows of one workgroup (one per lane, four waves)
@@ -283,6 +292,9 @@ hipError_t launch_scalar_in(const double* ref, ScalarGeom S, int planes, double*
 hipError_t launch_scalar_populations_out(const double* dev, ScalarGeom S, double* out, hipStream_t s);
 hipError_t launch_scalar_out(const double* dev, ScalarGeom S, int x0, int y0, int nxw, int nyw, int sx, int sy,
                              double* out, hipStream_t s);
+// The wall flux of the last substep (include/iblb.h iblb_get_scalar_wall_flux): out[x] through the wall below row 0,
+// out[ncol + x] through the wall above row ny - 1.
+hipError_t launch_scalar_wall_flux(const double* dev, ScalarGeom S, ScalarRule R, double* out, hipStream_t s);
 
 // q(u^t) of the current state for the flux column (added to *out).
 template <typename T>

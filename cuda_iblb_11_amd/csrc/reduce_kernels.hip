@@ -19,7 +19,7 @@ namespace iblb {
 
 namespace {
 
-constexpr int NQ = REDUCE_NQ, RS = REDUCE_RS;
+constexpr int RS = REDUCE_RS;
 
 __device__ __forceinline__ bool finite(double v) {
     return (__double_as_longlong(v) & 0x7ff0000000000000LL) != 0x7ff0000000000000LL;
@@ -55,8 +55,9 @@ __device__ __forceinline__ void empty_record(double* a) {
 }
 
 // HEAVY: vorticity or a stress component is requested (bits 3 .. 6); the light build carries neither
-// their code nor their accumulators.
-template <typename T, bool HEAVY>
+// their code nor their accumulators.  SCALAR: one of the scalar's quantities is requested (bits 12 .. 14,
+// quantities 11 .. 13 here); the builds without carry neither their code nor their accumulators.
+template <typename T, bool HEAVY, bool SCALAR>
 __global__ __launch_bounds__(REDUCE_ROWS) void reduce_pass1_kernel(const T* __restrict__ g, Layout L, Halo<T> H,
                                                                    FieldsArgs a, ReduceGeom q,
                                                                    double* __restrict__ scratch) {
@@ -70,8 +71,11 @@ __global__ __launch_bounds__(REDUCE_ROWS) void reduce_pass1_kernel(const T* __re
     const int y = a.y0 + (valid ? j : a.nyw - 1) * a.sy;
     const int il0 = cbi * q.cc, il1 = min(a.nxl, il0 + q.cc);
     const unsigned fields = a.fields;
-    auto wanted = [&](int k) { return (HEAVY || k < 3 || k > 6) && ((fields >> k) & 1u); };
-    auto slot = [&](int k) { return __builtin_popcount(fields & ((1u << k) - 1u)); };  // k-th set bit ascending
+    constexpr int NQ = SCALAR ? REDUCE_NQ + 3 : REDUCE_NQ;
+    auto bit = [](int k) { return k < REDUCE_NQ ? k : k - REDUCE_NQ + FIELD_SCALAR_BIT0; };  // quantity k's bit
+    auto wanted = [&](int k) { return (HEAVY || k < 3 || k > 6) && ((fields >> bit(k)) & 1u); };
+    // the place of quantity k in the output: the set bits below its own (ascending bit order)
+    auto slot = [&](int k) { return __builtin_popcount(fields & ((1u << bit(k)) - 1u)); };
 
     double sum[NQ], sq[NQ], mn[NQ], mx[NQ];
     int bad[NQ], mni[NQ], mxi[NQ];
@@ -90,8 +94,13 @@ __global__ __launch_bounds__(REDUCE_ROWS) void reduce_pass1_kernel(const T* __re
         double f[9], v[NQ];
 #pragma unroll
         for (int k = 0; k < NQ; ++k) v[k] = 0.;
-        cell_state<T>(g, L, H, a, xc, y, f, v[0], v[1], v[2]);
+        if (wants_fluid<SCALAR>(a)) cell_state<T>(g, L, H, a, xc, y, f, v[0], v[1], v[2]);
         const double r = v[0], ux = v[1], uy = v[2];
+        if constexpr (SCALAR) {
+            v[REDUCE_NQ] = cell_scalar(a, xc, y);
+            v[REDUCE_NQ + 1] = v[REDUCE_NQ] * ux;
+            v[REDUCE_NQ + 2] = v[REDUCE_NQ] * uy;
+        }
         if constexpr (HEAVY) {
             if (fields & IBLB_FIELD_VORT) v[3] = cell_vorticity<T>(g, L, H, a, xc, y, ux);
             if (fields & (IBLB_FIELD_SXX | IBLB_FIELD_SXY | IBLB_FIELD_SYY))
@@ -221,10 +230,13 @@ hipError_t launch_reduce_fields(const T* g, Layout L, Halo<T> H, const FieldsArg
                                 double* scratch, hipStream_t s) {
     if (a.nxl <= 0 || a.nyw <= 0) return hipErrorInvalidValue;
     const dim3 grid((unsigned)q.rb, (unsigned)q.cb);
-    if (a.fields & (IBLB_FIELD_VORT | IBLB_FIELD_SXX | IBLB_FIELD_SXY | IBLB_FIELD_SYY))
-        reduce_pass1_kernel<T, true><<<grid, REDUCE_ROWS, 0, s>>>(g, L, H, a, q, scratch);
-    else
-        reduce_pass1_kernel<T, false><<<grid, REDUCE_ROWS, 0, s>>>(g, L, H, a, q, scratch);
+    const bool heavy = a.fields & (IBLB_FIELD_VORT | IBLB_FIELD_SXX | IBLB_FIELD_SXY | IBLB_FIELD_SYY);
+    const bool scalar = a.fields & FIELD_SCALAR_BITS;
+    if (scalar && !a.sc) return hipErrorInvalidValue;
+    if (heavy && scalar) reduce_pass1_kernel<T, true, true><<<grid, REDUCE_ROWS, 0, s>>>(g, L, H, a, q, scratch);
+    else if (heavy) reduce_pass1_kernel<T, true, false><<<grid, REDUCE_ROWS, 0, s>>>(g, L, H, a, q, scratch);
+    else if (scalar) reduce_pass1_kernel<T, false, true><<<grid, REDUCE_ROWS, 0, s>>>(g, L, H, a, q, scratch);
+    else reduce_pass1_kernel<T, false, false><<<grid, REDUCE_ROWS, 0, s>>>(g, L, H, a, q, scratch);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     const long tail = (q.n_out - (long)q.nf * RS + 255) / 256;

@@ -141,6 +141,19 @@ __global__ __launch_bounds__(TILE * 8) void scalar_out_kernel(const double* __re
     }
 }
 
+// The wall flux of the last substep (include/iblb.h iblb_get_scalar_wall_flux): one lane per column, which reads
+// row 0 of plane 3 and row ny - 1 of plane 4 (2 * ncol loads a column stride apart: nothing to coalesce, and a
+// thousandth of a substep's traffic).  out[x]: the wall below row 0; out[ncol + x]: the wall above the top row.
+__global__ __launch_bounds__(256) void scalar_wall_flux_kernel(const double* __restrict__ dev, ScalarGeom S, ScalarRule R,
+                                                               double* __restrict__ out) {
+#pragma clang fp contract(off)
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (x >= S.ncol) return;
+    const double g3 = dev[3 * S.plane + (long)x * S.rows], g4 = dev[4 * S.plane + (long)x * S.rows + (S.ny - 1)];
+    out[x] = R.wall_kind[0] == IBLB_SCALAR_WALL_VALUE ? 2.0 * g3 - (2.0 * SW1) * R.wall_value[0] : 0.0;
+    out[S.ncol + x] = R.wall_kind[1] == IBLB_SCALAR_WALL_VALUE ? 2.0 * g4 - (2.0 * SW1) * R.wall_value[1] : 0.0;
+}
+
 inline bool geom_ok(const ScalarGeom& S) {
     return S.ncol > 0 && S.ny > 0 && S.rows >= S.ny && S.plane >= (long)S.ncol * S.rows;
 }
@@ -190,6 +203,12 @@ hipError_t launch_scalar_out(const double* dev, ScalarGeom S, int x0, int y0, in
                              double* out, hipStream_t s) {
     if (!geom_ok(S) || nxw < 1 || nyw < 1) return hipErrorInvalidValue;
     scalar_out_kernel<true><<<tile_grid(nxw, nyw, 1), dim3(TILE, 8), 0, s>>>(dev, S, x0, y0, nxw, nyw, sx, sy, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_scalar_wall_flux(const double* dev, ScalarGeom S, ScalarRule R, double* out, hipStream_t s) {
+    if (!geom_ok(S)) return hipErrorInvalidValue;
+    scalar_wall_flux_kernel<<<(unsigned)((S.ncol + 255) / 256), 256, 0, s>>>(dev, S, R, out);
     return hipGetLastError();
 }
 

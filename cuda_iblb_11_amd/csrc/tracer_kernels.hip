@@ -7,7 +7,8 @@
 // vorticity), served by the caches where neighbouring points share cells.  No atomics, no cross-lane
 // steps: every output value is a function of its own point and the state.  Each of the four cells is
 // evaluated by the device functions of field_eval.h, so a cell's value has the bits iblb_get_fields
-// returns for it; the interpolation is the header's expression, one rounding per operation.
+// returns for it; the interpolation is the header's expression, one rounding per operation.  With the scalar's
+// fields a cell costs five more loads, and C*ux, C*uy are formed per cell before they are interpolated.
 #include "field_eval.h"
 
 namespace iblb {
@@ -42,13 +43,18 @@ __device__ __forceinline__ double bilinear_mix(const Bilinear& q, double v00, do
 }
 
 // The selected fields of cell (xc, y), in the order of the IBLB_FIELD_* bits, as fields_out_kernel
-// (field_kernels.hip) evaluates them
-template <typename T>
+// (field_kernels.hip) evaluates them; SCALAR: then C, C*ux, C*uy (v[7 .. 9])
+template <typename T, bool SCALAR>
 __device__ __forceinline__ void cell_fields(const T* __restrict__ g, const Layout& L, const Halo<T>& H,
-                                            const FieldsArgs& a, int xc, int y, double v[7]) {
+                                            const FieldsArgs& a, int xc, int y, double* v) {
 #pragma clang fp contract(off)
-    double f[9], r, ux, uy;
-    cell_state<T>(g, L, H, a, xc, y, f, r, ux, uy);
+    double f[9], r = 0., ux = 0., uy = 0.;
+    if (wants_fluid<SCALAR>(a)) cell_state<T>(g, L, H, a, xc, y, f, r, ux, uy);
+    if constexpr (SCALAR) {
+        v[7] = cell_scalar(a, xc, y);
+        v[8] = v[7] * ux;
+        v[9] = v[7] * uy;
+    }
     v[0] = r;
     v[1] = ux;
     v[2] = uy;
@@ -57,8 +63,9 @@ __device__ __forceinline__ void cell_fields(const T* __restrict__ g, const Layou
     if (a.fields & (IBLB_FIELD_SXX | IBLB_FIELD_SXY | IBLB_FIELD_SYY)) cell_stress(f, r, ux, uy, a.kvisc, v[4], v[5], v[6]);
 }
 
-// out[k*n + p]: the k-th set bit of a.fields at point p = (xy[p], xy[n + p])
-template <typename T>
+// out[k*n + p]: the k-th set bit of a.fields at point p = (xy[p], xy[n + p]).  SCALAR: one of the scalar's
+// fields is requested (FIELD_SCALAR_BITS); the build without carries none of their code.
+template <typename T, bool SCALAR>
 __global__ __launch_bounds__(256) void sample_points_kernel(const T* __restrict__ g, Layout L, Halo<T> H, FieldsArgs a,
                                                             long n, const double* __restrict__ xy,
                                                             double* __restrict__ out) {
@@ -66,15 +73,16 @@ __global__ __launch_bounds__(256) void sample_points_kernel(const T* __restrict_
     const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
     const Bilinear q = bilinear_of(xy[p], xy[n + p], L.ncol, L.ny);
-    double v00[7], v10[7], v01[7], v11[7];
-    cell_fields<T>(g, L, H, a, q.i0, q.j0, v00);
-    cell_fields<T>(g, L, H, a, q.i1, q.j0, v10);
-    cell_fields<T>(g, L, H, a, q.i0, q.j1, v01);
-    cell_fields<T>(g, L, H, a, q.i1, q.j1, v11);
+    constexpr int NV = SCALAR ? 10 : 7;
+    double v00[NV], v10[NV], v01[NV], v11[NV];
+    cell_fields<T, SCALAR>(g, L, H, a, q.i0, q.j0, v00);
+    cell_fields<T, SCALAR>(g, L, H, a, q.i1, q.j0, v10);
+    cell_fields<T, SCALAR>(g, L, H, a, q.i0, q.j1, v01);
+    cell_fields<T, SCALAR>(g, L, H, a, q.i1, q.j1, v11);
     double* o = out + p;
 #pragma unroll
-    for (int k = 0; k < 7; ++k)
-        if (a.fields & (1u << k)) {
+    for (int k = 0; k < NV; ++k)
+        if (a.fields & (1u << (k < 7 ? k : k - 7 + FIELD_SCALAR_BIT0))) {
             *o = bilinear_mix(q, v00[k], v10[k], v01[k], v11[k]);
             o += n;
         }
@@ -122,7 +130,13 @@ template <typename T>
 hipError_t launch_sample_points(const T* g, Layout L, Halo<T> H, const FieldsArgs& a, long n, const double* xy,
                                 double* out, hipStream_t s) {
     if (n <= 0) return hipSuccess;
-    sample_points_kernel<T><<<(unsigned)((n + 255) / 256), 256, 0, s>>>(g, L, H, a, n, xy, out);
+    const unsigned grid = (unsigned)((n + 255) / 256);
+    if (a.fields & FIELD_SCALAR_BITS) {
+        if (!a.sc) return hipErrorInvalidValue;
+        sample_points_kernel<T, true><<<grid, 256, 0, s>>>(g, L, H, a, n, xy, out);
+    } else {
+        sample_points_kernel<T, false><<<grid, 256, 0, s>>>(g, L, H, a, n, xy, out);
+    }
     return hipGetLastError();
 }
 

@@ -305,17 +305,18 @@ class Lattice:
 
     def fields(self, names, window=None) -> dict:
         """Fields on a strided window, computed on the device and copied out at the window's size
-        (iblb_get_fields).  names: any of "rho", "ux", "uy", "vort", "sxx", "sxy", "syy"; returns
+        (iblb_get_fields).  names: any of "rho", "ux", "uy", "vort", "sxx", "sxy", "syy" and, with a
+        scalar set, "c", "cux", "cuy" (L.READ_FIELDS; C as `scalar` returns it, C*ux, C*uy); returns
         {name: array (ny, nx_local)} of this slab's samples (collective in an RCCL group)."""
         names = [names] if isinstance(names, str) else list(names)
-        unknown = [n for n in names if n not in L.FIELDS]
+        unknown = [n for n in names if n not in L.READ_FIELDS]
         if unknown or not names:
-            raise ValueError(f"fields must be chosen from {sorted(L.FIELDS)}, got {names}")
+            raise ValueError(f"fields must be chosen from {sorted(L.READ_FIELDS)}, got {names}")
         w = _window(window)
         _, nxl = self.window_local(w)
         ny = self.ny if w is None else w.ny
-        order = sorted(set(names), key=L.FIELDS.get)
-        bits = sum(L.FIELDS[n] for n in order)
+        order = sorted(set(names), key=L.READ_FIELDS.get)
+        bits = sum(L.READ_FIELDS[n] for n in order)
         out = np.empty((len(order), ny, nxl))
         self._check(self._lib.iblb_get_fields(self._h, None if w is None else C.byref(w), bits, _ptr(out)))
         return {n: out[k] for k, n in enumerate(order)}
@@ -323,7 +324,7 @@ class Lattice:
     def reduce(self, names, window=None, rows=False, cols=False) -> dict:
         """Statistics of quantities over a strided window, reduced on the device (iblb_reduce_fields):
         nothing of the window's size is copied.  names: any of L.QUANTITIES (the fields of `fields`
-        plus "momx", "momy", "ke", "usq"); returns {name: Stats} in ascending bit order, for this
+        plus "momx", "momy", "ke", "usq"; "c", "cux", "cuy" last); returns {name: Stats} in ascending bit order, for this
         slab's samples (collective in an RCCL group).  rows / cols: also the sums over this slab's i
         of every window row (Stats.row_sum) / over j of every sample column (Stats.col_sum)."""
         names = [names] if isinstance(names, str) else list(names)
@@ -349,15 +350,15 @@ class Lattice:
         names as for `fields`; x, y: global lattice coordinates, 0 <= x < nx (periodic), 0 <= y <= ny-1.
         Returns {name: array [n]} in ascending bit order.  A lone slab only."""
         names = [names] if isinstance(names, str) else list(names)
-        unknown = [n for n in names if n not in L.FIELDS]
+        unknown = [n for n in names if n not in L.READ_FIELDS]
         if unknown or not names:
-            raise ValueError(f"fields must be chosen from {sorted(L.FIELDS)}, got {names}")
+            raise ValueError(f"fields must be chosen from {sorted(L.READ_FIELDS)}, got {names}")
         x = np.ascontiguousarray(x, dtype=np.float64).ravel()
         y = np.ascontiguousarray(y, dtype=np.float64).ravel()
         if x.size != y.size:
             raise ValueError("x and y must hold the same number of points")
-        order = sorted(set(names), key=L.FIELDS.get)
-        bits = sum(L.FIELDS[n] for n in order)
+        order = sorted(set(names), key=L.READ_FIELDS.get)
+        bits = sum(L.READ_FIELDS[n] for n in order)
         out = np.empty((len(order), x.size))
         self._check(self._lib.iblb_sample_points(self._h, x.size, _ptr(x), _ptr(y), bits, _ptr(out)))
         return {n: out[k] for k, n in enumerate(order)}
@@ -394,14 +395,14 @@ class Lattice:
         sums of v*v; uxuy: also the sum of ux*uy (needs "ux" and "uy").  Empty names remove
         averaging.  A lone slab only."""
         names = [names] if isinstance(names, str) else list(names)
-        unknown = [n for n in names if n not in L.FIELDS]
+        unknown = [n for n in names if n not in L.READ_FIELDS]
         if unknown:
-            raise ValueError(f"fields must be chosen from {sorted(L.FIELDS)}, got {names}")
+            raise ValueError(f"fields must be chosen from {sorted(L.READ_FIELDS)}, got {names}")
         if not names:
             self._check(self._lib.iblb_set_average(self._h, None, 0, 1, 1, 0))
             return
         w = _window(window)
-        bits = sum(L.FIELDS[n] for n in set(names))
+        bits = sum(L.READ_FIELDS[n] for n in set(names))
         flags = (L.AVG_SQ if squares else 0) | (L.AVG_UXUY if uxuy else 0)
         self._check(self._lib.iblb_set_average(self._h, None if w is None else C.byref(w), bits, int(stride),
                                                int(nbins), flags))
@@ -419,7 +420,7 @@ class Lattice:
         self._check(self._lib.iblb_average_info(self._h, C.byref(w), C.byref(fields), C.byref(stride), C.byref(nbins),
                                                 C.byref(flags), C.byref(total)))
         return {"window": (w.x0, w.y0, w.nx, w.ny, w.sx, w.sy), "fields": fields.value,
-                "names": [n for n, b in L.FIELDS.items() if fields.value & b], "stride": stride.value,
+                "names": [n for n, b in L.READ_FIELDS.items() if fields.value & b], "stride": stride.value,
                 "nbins": nbins.value, "flags": flags.value, "samples_total": total.value}
 
     def average(self, bin: int = 0) -> dict:
@@ -485,6 +486,13 @@ class Lattice:
         out = np.empty(shape)
         self._check(self._lib.iblb_get_scalar(self._h, None if w is None else C.byref(w), _ptr(out)))
         return out
+
+    def scalar_wall_flux(self) -> tuple[np.ndarray, np.ndarray]:
+        """(bottom, top), [nx] each: the net amount of C that entered every column through the wall below row 0 /
+        above the top row during the last substep (iblb_get_scalar_wall_flux); exact zeros at a no-flux wall."""
+        bottom, top = np.empty(self.x_count), np.empty(self.x_count)
+        self._check(self._lib.iblb_get_scalar_wall_flux(self._h, _ptr(bottom), _ptr(top)))
+        return bottom, top
 
     def scalar_populations(self) -> np.ndarray:
         """The five post-stream populations, (5, ny, nx) (iblb_get_scalar_populations): what `set_scalar(g0=...)`

@@ -267,6 +267,22 @@ typedef struct iblb_window { int x0, y0, nx, ny, sx, sy; } iblb_window;   /* glo
 #define IBLB_FIELD_SXX 16  /* viscous stress -(1 - 1/(2 TAU)) * PiNeq_ab */
 #define IBLB_FIELD_SXY 32
 #define IBLB_FIELD_SYY 64
+/* The passive scalar (iblb_set_scalar below) through the same readers; bits 128 .. 1024 are iblb_reduce_fields'
+ * own quantities and 2048 is no bit.  Each is defined bit-exactly, in double, one rounding per operation, no
+ * contraction:
+ *   C   = (((g0+g1)+g2)+g3)+g4 of the scalar's stored populations at the moment of the call: what iblb_get_scalar
+ *         returns for that cell, bit for bit.  Between two events of the scalar it is the C of the last event,
+ *         while ux, uy are those of the current state.
+ *   CUX = C*ux, CUY = C*uy with ux, uy the IBLB_FIELD_UX / _UY values of that cell at that moment.
+ * Accepted by iblb_get_fields, iblb_reduce_fields, iblb_sample_points (the product is formed per cell, then
+ * interpolated) and iblb_set_average (which adds v, and v*v under IBLB_AVG_SQ, as for any field: <ux C> is the
+ * sum plane of IBLB_FIELD_CUX), ordered with the other bits by ascending bit, in every phase.  With no scalar
+ * set, and always on a slab of a local or RCCL group (which cannot hold one), a request with one of these bits
+ * returns IBLB_ERR_STATE: checked after the argument checks and the vorticity check below, before anything
+ * collective or any launch, no output touched. */
+#define IBLB_FIELD_C   4096   /* the passive scalar, as iblb_get_scalar returns it for that cell */
+#define IBLB_FIELD_CUX 8192   /* C*ux : advective flux density, one rounding */
+#define IBLB_FIELD_CUY 16384  /* C*uy */
 /* The samples of window w whose column this context owns: sample indices [*i_first, *i_first +
  * *nx_local) of the window's nx (nx_local may be 0; either pointer may be NULL). */
 int iblb_window_local(iblb_ctx* ctx, const iblb_window* w, int* i_first, int* nx_local);
@@ -287,8 +303,8 @@ int iblb_window_local(iblb_ctx* ctx, const iblb_window* w, int* i_first, int* nx
 int iblb_get_fields(iblb_ctx* ctx, const iblb_window* w, unsigned fields, double* out);
 
 /* Window reduction: statistics, row sums and column sums of chosen quantities over a window, computed on
- * the device; what crosses to the host is O(nx + ny) values, not the window.  `w`, the seven IBLB_FIELD_*
- * bits and the value of every sample are exactly those of iblb_get_fields (every phase, the boot phase
+ * the device; what crosses to the host is O(nx + ny) values, not the window.  `w`, the IBLB_FIELD_* bits (the
+ * scalar's three included) and the value of every sample are exactly those of iblb_get_fields (every phase, the boot phase
  * included); four more quantities are accepted here only (iblb_get_fields refuses them), each the stated
  * expression of that sample's rho, ux, uy with one rounding per operation: */
 #define IBLB_QTY_MOMX 128    /* rho*ux */
@@ -322,7 +338,7 @@ int iblb_reduce_fields(iblb_ctx* ctx, const iblb_window* w, unsigned fields, ibl
 
 /* Point sampling: chosen fields at n arbitrary points, interpolated on the device; the points cross in one
  * copy and the results return in one.  x, y [n] are host arrays in global lattice coordinates, `fields` the
- * seven IBLB_FIELD_* bits, out[k*n + p] the k-th set bit (ascending) at point p.  A point needs 0 <= x < XDIM
+ * IBLB_FIELD_* bits of iblb_get_fields, out[k*n + p] the k-th set bit (ascending) at point p.  A point needs 0 <= x < XDIM
  * and 0 <= y <= YDIM-1, both finite.  With
  *   i0 = floor(x), i1 = (i0 + 1) mod XDIM (periodic), a = x - i0,
  *   j0 = min(floor(y), YDIM-2), j1 = j0 + 1, b = y - j0  (y = YDIM-1: b = 1 on the top row)
@@ -368,7 +384,7 @@ int iblb_tracer_count(iblb_ctx* ctx, long long* n, int* stride, long long* updat
 /* Time- and phase-averaged fields: sums of chosen fields over a window that the context itself accumulates
  * on the device while iblb_step runs, so that a beat average (the mean flow, its fluctuation <u'u'>, the flow
  * at a given phase of the beat) needs no readback per sample and keeps the deep sweep between samples.
- * `w` and `fields` are those of iblb_get_fields (the seven IBLB_FIELD_* bits; NULL = the whole lattice at
+ * `w` and `fields` are those of iblb_get_fields (the IBLB_FIELD_* bits; NULL = the whole lattice at
  * stride 1); stride >= 1, nbins >= 1; flags: */
 #define IBLB_AVG_SQ   1   /* also accumulate v*v of every requested field            */
 #define IBLB_AVG_UXUY 2   /* also accumulate ux*uy (needs IBLB_FIELD_UX and _UY)      */
@@ -389,8 +405,10 @@ int iblb_tracer_count(iblb_ctx* ctx, long long* n, int* stride, long long* updat
  * iblb_step(nsteps) with averaging cuts the call at the sample iterations and schedules each piece (at most
  * `stride` iterations) as a call of its own; the result is by definition that of the caller doing
  * iblb_step(piece), then iblb_get_fields, then adding on the host.  Samples count on across calls.  With
- * tracers set as well the call is cut at the union of both event sets; at a common iteration both run, and
- * since neither changes the state their order is free.  A stride >= K (IBLB_SWEEP_DEPTH) keeps the deep sweep
+ * tracers set as well the call is cut at the union of both event sets; at a common iteration both run (the
+ * order of every observer: iblb_set_scalar below).  A scalar bit needs a scalar at the call (IBLB_ERR_STATE, the
+ * previous set kept) and at every sample: iblb_set_scalar refuses to remove the scalar meanwhile, replacing it is
+ * allowed and the average goes on with the new one.  A stride >= K (IBLB_SWEEP_DEPTH) keeps the deep sweep
  * between samples; stride 1 costs the one-step path at every iteration.  One sample is one launch on the
  * context's stream, one lane per window sample, without a host synchronise.
  * iblb_reset_average zeroes the sums and counts and sets t0 to the current step (the next sample is number 0,
@@ -447,7 +465,10 @@ typedef struct iblb_scalar {
  * Nothing is filtered: a non-finite value spreads.  The scheme conserves sum(C) between no-flux walls, and diffuses
  * with D = (tau - 0.5)/3 (its error grows towards tau = 0.5 and with the cell Peclet number |u|/D).
  * iblb_step(nsteps) with a scalar cuts the call at the union of the scalar's, the tracers' and the averages' event
- * sets; at a common iteration all due observers run, and since none changes the fluid state their order is free.  A
+ * sets; at a common iteration all due observers run: the scalar's event first, then the tracers' update and the
+ * averages' sample, so that a sample of IBLB_FIELD_C / _CUX / _CUY sees C after that iteration's event (for every
+ * other field the order cannot be observed: no observer changes the fluid state).  cfg == NULL while the current
+ * average holds a scalar bit: IBLB_ERR_STATE, nothing changed (remove or replace the average first).  A
  * stride >= K (IBLB_SWEEP_DEPTH) keeps the deep sweep between events; stride 1 costs the one-step path at every
  * iteration.  A substep is one launch on the context's stream, one lane per cell, 96 bytes per cell, without a host
  * synchronise.
@@ -459,11 +480,19 @@ typedef struct iblb_scalar {
  * iblb_set_state keeps the scalar (populations and event count) and re-bases t0 to the new state's step count 0.
  * Checkpoints do not hold the scalar: iblb_load_checkpoint removes it; the caller saves it with
  * iblb_get_scalar_populations and restores it through g0.  A context that joins a group after the set fails its
- * next event with IBLB_ERR_UNSUPPORTED.  iblb_destroy frees the scalar. */
+ * next event with IBLB_ERR_UNSUPPORTED.  iblb_destroy frees the scalar.
+ * iblb_get_scalar_wall_flux.  bottom[x], top[x], x < XDIM (either may be NULL, not both): the net amount of C that
+ * entered column x through that wall during the last substep, from the stored populations:
+ *   _VALUE:  bottom[x] = 2.0*g3(x,0) - (2.0*w1)*wall_value[0];  top[x] = 2.0*g4(x,YDIM-1) - (2.0*w1)*wall_value[1]
+ *   _NOFLUX: 0.0 exactly.   w1 = 1.0/6.0.   Before any substep it is merely this expression of g0.
+ * (Anti-bounce-back stores g3' = 2 w1 Cw - p4: what entered minus what left is g3' - p4 = 2 g3' - 2 w1 Cw, so the
+ * sum over x of bottom + top is the change of sum(C) over that substep up to rounding.)
+ * No scalar: IBLB_ERR_STATE; both NULL: IBLB_ERR_ARG. */
 int iblb_set_scalar(iblb_ctx* ctx, const iblb_scalar* cfg, const double* c0, const double* g0);
 int iblb_get_scalar(iblb_ctx* ctx, const iblb_window* w, double* c);
 int iblb_get_scalar_populations(iblb_ctx* ctx, double* g);
 int iblb_scalar_info(iblb_ctx* ctx, iblb_scalar* cfg, long long* updates);
+int iblb_get_scalar_wall_flux(iblb_ctx* ctx, double* bottom, double* top);
 
 /* Timing: when enabled (1) every collide-stream launch is bracketed by HIP events on the
  * stream it runs on; iblb_get_timing() returns the sums (and resets them if reset).  enabled = 2:
