@@ -168,6 +168,7 @@ _SIGS = {
     "iblb_set_profiling": ([_vp, C.c_int], C.c_int),
     "iblb_get_timing": ([_vp, C.POINTER(Timing), C.c_int], C.c_int),
     "iblb_get_timing_ex": ([_vp, C.POINTER(Timing), C.c_ulong, C.c_int], C.c_int),
+    "iblb_deep_force_build": ([_vp], C.c_int),
     "iblb_get_stream": ([_vp, C.POINTER(_vp)], C.c_int),
     "iblb_synchronize": ([_vp], C.c_int),
     "iblb_link_local": ([C.POINTER(_vp), C.c_int], C.c_int),

@@ -1,6 +1,7 @@
 // deep_plan.h — the host decisions of a deep-sweep launch (sweepk_kernel, lbm_sweep_impl.h): the row
 // geometry, which kernel builds exist and which one a launch takes, how many sweeps and waves it gets,
-// how many of its waves are edge waves, and the depth mix of a call.  Pure functions, standard C++
+// how many of its waves are edge waves, the depth mix of a call, and whether the collide's build for a
+// body force along x only applies (tests/deep_force_main.cpp).  Pure functions, standard C++
 // only: no HIP, no Sweep2Args, so that a CPU build can check them (tests/deep_plan_main.cpp,
 // tests/test_deep_plan.py).  lbm_sweep_impl.h's launchers apply them and own the occupancy query and
 // the launch; sweepk_kernel restates sweep_range and the row split on the device (the two must agree:
@@ -20,6 +21,8 @@ struct DeepBuild {
     bool split;   // the wall-row chunks as their own sweep family (one cell per lane), the inner chunks preshifted
     bool pack;    // f32, two cells per lane: both cells' collides as one packed f32x2 computation
     bool window;  // two cells per lane, split: the moving populations wait in an LDS window
+    // not a feature of deep_choose's: the collide's force axis (below) held at the general build
+    bool general_force = false;
 };
 
 // sweep only (MODE bits 1, 2, 4 as in lbm_vec.h; bit 0, nontemporal stores, is in every deep build):
@@ -232,6 +235,20 @@ inline bool parse_deep_build(const char* e, DeepBuild* out) {
             i = j + 1;
         }
     *out = b;
+    return true;
+}
+
+// ---- the collide's force axis ----
+// The deep sweep's collide has a second build for a body force along x only (XF, relax_cells /
+// relax_dev in iblb_device.h): the launcher takes it when the launch's force constants allow it.
+// F_y = +0 or -0 does; a NaN or a denormal F_y does not.
+constexpr bool deep_force_x_only(double fx, double fy) { return (void)fx, fy == 0.0; }
+
+// IBLB_DEEP_FORCE: the one word general (the general collide whatever the force: the tests' and the
+// same-library comparison's knob)
+inline bool parse_deep_force(const char* e, bool* general) {
+    if (std::string(e) != "general") return false;
+    *general = true;
     return true;
 }
 

@@ -295,6 +295,11 @@ int iblb_create(const iblb_config* cfg, iblb_ctx** out) {
     if (const char* e = std::getenv("IBLB_DEEP_BUILD"))
         if (!parse_deep_build(e, &deep_build))
             return fail(nullptr, IBLB_ERR_ARG, "IBLB_DEEP_BUILD: expected a comma list of split, pack, window, or plain");
+    // IBLB_DEEP_FORCE=general: the deep sweeps' general collide although the body force is along x only
+    // (the tests' knob, and the same-library comparison's)
+    if (const char* e = std::getenv("IBLB_DEEP_FORCE"))
+        if (!parse_deep_force(e, &deep_build.general_force))
+            return fail(nullptr, IBLB_ERR_ARG, "IBLB_DEEP_FORCE: expected general");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail(nullptr, IBLB_ERR_NODEVICE, "no HIP device visible (the HIP path has no CPU fallback)");
@@ -680,6 +685,8 @@ int iblb_get_timing_ex(iblb_ctx* c, iblb_timing* out, unsigned long bytes, int r
     std::memcpy(out, &full, std::min((size_t)bytes, sizeof(full)));
     return IBLB_OK;
 }
+
+int iblb_deep_force_build(const iblb_ctx* c) { return c ? c->deep_kinfo[4] : -1; }
 
 int iblb_get_stream(iblb_ctx* c, void** stream) {
     if (!c || !stream) return IBLB_ERR_ARG;

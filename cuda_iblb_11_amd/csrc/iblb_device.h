@@ -288,13 +288,14 @@ __device__ __forceinline__ float recip(float x) {
 // broadcast from scalar registers).  The same operations in the same order per element, so both
 // round every cell identically: the deep sweep's packed walk stays bit-identical to the one-step
 // kernels.  rho-free odd part and rho-scaled constants as collide_sd's JM.
+// XF: the build for a body force along x only (relax_cells below has the argument).
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float vfma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 __device__ __forceinline__ f32x2 vfma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ float vrcp(float x) { return __builtin_amdgcn_rcpf(x); }
 __device__ __forceinline__ f32x2 vrcp(f32x2 x) { return f32x2{__builtin_amdgcn_rcpf(x.x), __builtin_amdgcn_rcpf(x.y)}; }
 
-template <typename V>
+template <typename V, bool XF = false>
 __device__ __forceinline__ V relax_dev(V f[9], const KBase<float>& b, const KForce<float>& k) {
 #pragma clang fp contract(off)
     V s[4], d[4];
@@ -309,10 +310,10 @@ __device__ __forceinline__ V relax_dev(V f[9], const KBase<float>& b, const KFor
     const V rho = (V)1.f + sum;
     V inv = vrcp(rho);  // + one Newton step (recip(float))
     inv = vfma(inv, vfma(-rho, inv, (V)1.f), inv);
-    const V jx = mx + (V)k.hFx, jy = my + (V)k.hFy;
+    const V jx = mx + (V)k.hFx, jy = XF ? my : my + (V)k.hFy;
     const V ux = jx * inv, uy = jy * inv;
     const V usq = vfma(uy, uy, ux * ux);
-    const V uF = vfma(uy, (V)k.Fy, ux * (V)k.Fx);
+    const V uF = XF ? ux * (V)k.Fx : vfma(uy, (V)k.Fy, ux * (V)k.Fx);
     const V base = -usq * (V)b.a1;
     const V rb = vfma(rho, base, sum);
     f[0] = vfma((V)b.omp, f[0], rb * (V)b.opw0);
@@ -327,8 +328,17 @@ __device__ __forceinline__ V relax_dev(V f[9], const KBase<float>& b, const KFor
         const int cl = p < 2 ? 0 : 1;
         const V cu = p == 0 ? ux : (p == 1 ? uy : (p == 2 ? ux + uy : uy - ux));
         const V cj = p == 0 ? jx : (p == 1 ? jy : (p == 2 ? jx + jy : jy - jx));
-        const V E = vfma(cu, vfma(Qa[cl], cu, (V)k.hE[p]), P[cl]);
-        const V O = vfma((V)b.omwi2[cl], cj, (V)k.gO[p]);
+        V E, O;
+        if (XF && p == 1) {
+            E = vfma(cu, Qa[cl] * cu, P[cl]);
+            O = (V)b.omwi2[cl] * cj;
+        } else if (XF && p == 3) {
+            E = vfma(cu, vfma(Qa[cl], cu, (V)-k.hE[2]), P[cl]);
+            O = vfma((V)b.omwi2[cl], cj, (V)-k.gO[2]);
+        } else {
+            E = vfma(cu, vfma(Qa[cl], cu, (V)k.hE[p]), P[cl]);
+            O = vfma((V)b.omwi2[cl], cj, (V)k.gO[p]);
+        }
         const V A = vfma(s[p], (V)b.hs, E);
         const V B = vfma(d[p], (V)b.hd, O);
         f[pair_a(p)] = A + B;
@@ -375,7 +385,18 @@ __device__ __forceinline__ R relax_cell(R f[9], const KBase<R>& b, const KForce<
 // fma(a, a, b*b) there), so every cell rounds as in the one-step kernels.  The constants stay scalar
 // operands of scalar statements (as a two-element vector computation the compiler splats them into
 // vector registers and spills: 295 SGPR spills against 131).
-template <int N>
+// XF: the build for a body force along x only, F_y = +-0 (deep_plan.h: deep_force_x_only; the deep
+// sweep's launcher takes it from the launch's constants).  The same operations in the same order,
+// without the ones whose operand is the zero, and reading six of KForce's twelve constants (Fx, hFx,
+// hE[0], hE[2], gO[0], gO[2]: the others are dead kernel arguments, so fewer SGPR reloads in the
+// loops): jy = my, uF = ux Fx, pair 1 without hE[1] and gO[1], pair 3 with -hE[2] and -gO[2].  Every
+// population comes out bit for bit as from the general build:
+//   x + (+-0) = x for x != -0, and my, a sum of differences a - b, is never -0;
+//   fma(a, b, +-0) and a b differ only in the sign of a zero result, and that sign reaches P, E and B
+//   only as an addend beside a nonzero term (rb opw; P; A), which it does not change;
+//   make_kforce's (0 - Fx) c = -(Fx c) and (Fx + 0) c = Fx c exactly, so hE[3] = -hE[2], gO[3] = -gO[2]
+//   (tests/test_deep_force.py checks the constants, tests/test_gpu_deep_force.py the populations).
+template <int N, bool XF = false>
 __device__ __forceinline__ void relax_cells(double (&f)[N][9], const KBase<double>& b, const KForce<double>& k,
                                             double (&ux)[N]) {
 #pragma clang fp contract(off)
@@ -402,16 +423,26 @@ __device__ __forceinline__ void relax_cells(double (&f)[N][9], const KBase<doubl
     IBLB_EACH nr[e] = __builtin_fma(-rho[e], inv[e], 1.0);  // (recip's two Newton steps)
     IBLB_EACH inv[e] = __builtin_fma(inv[e], nr[e], inv[e]);
     IBLB_EACH jx[e] = mx[e] + k.hFx;
-    IBLB_EACH jy[e] = my[e] + k.hFy;
+    if constexpr (XF) {
+        IBLB_EACH jy[e] = my[e];
+    } else {
+        IBLB_EACH jy[e] = my[e] + k.hFy;
+    }
     IBLB_EACH nr[e] = __builtin_fma(-rho[e], inv[e], 1.0);
     IBLB_EACH inv[e] = __builtin_fma(inv[e], nr[e], inv[e]);
     IBLB_EACH ux[e] = jx[e] * inv[e];
     IBLB_EACH uy[e] = jy[e] * inv[e];
     double usq[N], uF[N], rb[N], P[N][2], Qa[N][2], Rm[N][2];
     IBLB_EACH usq[e] = uy[e] * uy[e];
-    IBLB_EACH uF[e] = uy[e] * k.Fy;
+    if constexpr (!XF) {
+        IBLB_EACH uF[e] = uy[e] * k.Fy;
+    }
     IBLB_EACH usq[e] = __builtin_fma(ux[e], ux[e], usq[e]);
-    IBLB_EACH uF[e] = __builtin_fma(ux[e], k.Fx, uF[e]);
+    if constexpr (XF) {
+        IBLB_EACH uF[e] = ux[e] * k.Fx;
+    } else {
+        IBLB_EACH uF[e] = __builtin_fma(ux[e], k.Fx, uF[e]);
+    }
     IBLB_EACH rb[e] = -usq[e] * b.a1;
     IBLB_EACH rb[e] = 1.0 + rb[e];
     IBLB_EACH rb[e] = rho[e] * rb[e];
@@ -429,8 +460,17 @@ __device__ __forceinline__ void relax_cells(double (&f)[N][9], const KBase<doubl
         for (int p = 0; p < 4; ++p) {
             const int cl = p < 2 ? 0 : 1;
             const double cu = p == 0 ? ux[e] : (p == 1 ? uy[e] : (p == 2 ? ux[e] + uy[e] : uy[e] - ux[e]));
-            const double E = __builtin_fma(cu, __builtin_fma(Qa[e][cl], cu, k.hE[p]), P[e][cl]);
-            const double O = __builtin_fma(Rm[e][cl], cu, k.gO[p]);
+            double E, O;
+            if (XF && p == 1) {
+                E = __builtin_fma(cu, Qa[e][cl] * cu, P[e][cl]);
+                O = Rm[e][cl] * cu;
+            } else if (XF && p == 3) {
+                E = __builtin_fma(cu, __builtin_fma(Qa[e][cl], cu, -k.hE[2]), P[e][cl]);
+                O = __builtin_fma(Rm[e][cl], cu, -k.gO[2]);
+            } else {
+                E = __builtin_fma(cu, __builtin_fma(Qa[e][cl], cu, k.hE[p]), P[e][cl]);
+                O = __builtin_fma(Rm[e][cl], cu, k.gO[p]);
+            }
             const double A = __builtin_fma(s[e][p], b.hs, E);
             const double B = __builtin_fma(d[e][p], b.hd, O);
             f[e][pair_a(p)] = A + B;

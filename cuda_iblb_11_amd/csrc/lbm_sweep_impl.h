@@ -524,13 +524,13 @@ __device__ __forceinline__ void load_raw_periodic(const Sweep2Args<T>& a, int x,
 // f32, two cells per lane: both cells' collides as one packed f32x2 computation (relax_dev)
 template <typename T, int VS, int MODE>
 constexpr bool packed_pair() { return sizeof(T) == 4 && VS == 2 && (MODE & MODE_PACK); }
-template <typename T, int VS>
+template <typename T, int VS, bool XF>
 __device__ __forceinline__ void relax_pair(const T (&s)[9][VS], const Sweep2Args<T>& a, bool flux, int fown, double& q,
                                            T (&out)[9][VS]) {
     f32x2 f[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) f[k] = f32x2{(float)s[k][0], (float)s[k][1]};
-    const f32x2 ux = relax_dev<f32x2>(f, kbase<float>(a.k), kbody<float>(a.k));
+    const f32x2 ux = relax_dev<f32x2, XF>(f, kbase<float>(a.k), kbody<float>(a.k));
     if (flux) {  // wave-uniform branch; the lane condition as a select (no exec-mask branch)
         const double t0 = (double)ux.x / a.flux_norm, t1 = (double)ux.y / a.flux_norm;
         q += (fown & 1) ? t0 : 0.;
@@ -552,7 +552,7 @@ __device__ __forceinline__ void relax_pair(const T (&s)[9][VS], const Sweep2Args
 // one-cell wall walks.
 template <typename T, int VS, int MODE>
 constexpr bool lockstep_pair() { return sizeof(T) == 8 && VS == 2 && (MODE & MODE_LDSWIN); }
-template <typename T, int VS>
+template <typename T, int VS, bool XF>
 __device__ __forceinline__ void relax_lockstep(const T (&s)[9][VS], const Sweep2Args<T>& a, bool flux, int fown,
                                                double& q, T (&out)[9][VS]) {
     double f[VS][9], ux[VS];
@@ -560,7 +560,7 @@ __device__ __forceinline__ void relax_lockstep(const T (&s)[9][VS], const Sweep2
     for (int k = 0; k < 9; ++k)
 #pragma unroll
         for (int e = 0; e < VS; ++e) f[e][k] = (double)s[k][e];
-    relax_cells<VS>(f, kbase<double>(a.k), kbody<double>(a.k), ux);
+    relax_cells<VS, XF>(f, kbase<double>(a.k), kbody<double>(a.k), ux);
     if (flux) {  // wave-uniform branch; the lane condition as a select (no exec-mask branch)
 #pragma unroll
         for (int e = 0; e < VS; ++e) {
@@ -578,7 +578,8 @@ __device__ __forceinline__ void relax_lockstep(const T (&s)[9][VS], const Sweep2
 // walking direction DX): the output is B's column; flux: add u_x of the owned rows to q
 // ASH: A's populations that wait in the LDS window arrive already at their pull's rows
 // (lds_pop_read); the others are pulled as usual (LDS window only: no wall rows in those waves)
-template <typename T, int VS, int DX, int MODE = 0, bool ASH = false>
+// XF: the lock-step and packed collides in their build for a body force along x only (relax_cells)
+template <typename T, int VS, int DX, int MODE = 0, bool ASH = false, bool XF = false>
 __device__ __forceinline__ void level_from_window(const T (&A)[9][VS], const T (&B)[9][VS], const T (&C)[9][VS],
                                                   const Sweep2Args<T>& a, int lane, int r0, int et, bool walls,
                                                   bool flux, int fown, double& q, T (&out)[9][VS]) {
@@ -597,11 +598,11 @@ __device__ __forceinline__ void level_from_window(const T (&A)[9][VS], const T (
                 for (int e = 0; e < VS; ++e) s[k][e] = A[k][e];
     }
     if constexpr (packed_pair<T, VS, MODE>()) {
-        relax_pair<T, VS>(s, a, flux, fown, q, out);
+        relax_pair<T, VS, XF>(s, a, flux, fown, q, out);
         return;
     }
     if constexpr (lockstep_pair<T, VS, MODE>()) {
-        relax_lockstep<T, VS>(s, a, flux, fown, q, out);
+        relax_lockstep<T, VS, XF>(s, a, flux, fown, q, out);
         return;
     }
 #pragma unroll
@@ -620,7 +621,7 @@ __device__ __forceinline__ void level_from_window(const T (&A)[9][VS], const T (
 }
 
 // level 1 of one column from its loaded g^t rows
-template <typename T, int VS, int MODE = 0>
+template <typename T, int VS, int MODE = 0, bool XF = false>
 __device__ __forceinline__ void level_from_raw(const Raw<T, VS>& cur, const Sweep2Args<T>& a, int lane, int r0, int et,
                                                bool walls, bool flux, int fown, double& q, T (&out)[9][VS]) {
     typedef typename Calc<T>::R R;
@@ -656,11 +657,11 @@ __device__ __forceinline__ void level_from_raw(const Raw<T, VS>& cur, const Swee
         pull_window<T, VS>(pk, cur.e, cur.v[2], cur.v[4], cur.w[0], cur.w[1], t5, t6, lane, r0, et, s, walls);
     }
     if constexpr (packed_pair<T, VS, MODE>()) {
-        relax_pair<T, VS>(s, a, flux, fown, q, out);
+        relax_pair<T, VS, XF>(s, a, flux, fown, q, out);
         return;
     }
     if constexpr (lockstep_pair<T, VS, MODE>()) {
-        relax_lockstep<T, VS>(s, a, flux, fown, q, out);
+        relax_lockstep<T, VS, XF>(s, a, flux, fown, q, out);
         return;
     }
 #pragma unroll
@@ -803,7 +804,9 @@ constexpr bool step_ranges() { return lds_window<T, VS, MODE, WL>() && sizeof(T)
 // select against the old one at the loop's back edge (18 v_mov_b64 per f64 step)
 // STEADY (round 9; the walk's step ranges, sweepk_walk): a step on which every level is made and none stands
 // on the flux column: no `made` test, no flux test, the step one basic block.
-template <typename T, int VS, int MODE, int K, bool SLAB, bool REV, bool LW, bool UL = false, bool STEADY = false>
+// XF: the walk's collides built for a body force along x only (relax_cells; sweepk_kernel)
+template <typename T, int VS, int MODE, int K, bool SLAB, bool REV, bool LW, bool UL = false, bool STEADY = false,
+          bool XF = false>
 __device__ __forceinline__ void sweepk_iter(const Sweep2Args<T>& a, int i, int nl1, int x0, int xa, int xb, int row0,
                                             unsigned off, int lane, int r0, int et, bool owner, bool bot, bool top,
                                             bool walls, T (&WA)[K - 1][9][VS], T (&WB)[K - 1][9][VS],
@@ -840,7 +843,7 @@ __device__ __forceinline__ void sweepk_iter(const Sweep2Args<T>& a, int i, int n
         for (int p = 0; p < lds_npop<T>(); ++p) pre[p] = lds_pop_read<T, VS>(lds_slot(2) + p * 64, lds_cy(p));
     }
     // fin: the flux column is one of the sweep's outputs; level l reaches it at step fi + l - 1
-    level_from_raw<T, VS, MODE>(cur, a, lane, r0, et, walls, fin && i == fi, fown, q, N);
+    level_from_raw<T, VS, MODE, XF>(cur, a, lane, r0, et, walls, fin && i == fi, fown, q, N);
     if (UL || i + 1 < nl1) {
         // the resources of the next column triple: one new column
         const int xl = UL && i + 1 >= nl1 ? x - DX : x;
@@ -891,7 +894,8 @@ __device__ __forceinline__ void sweepk_iter(const Sweep2Args<T>& a, int i, int n
                     for (int p2 = 0; p2 < lds_npop<T>(); ++p2) pre[p2] = lds_pop_read<T, VS>(lds_slot(l + 1) + p2 * 64, lds_cy(p2));
                 }
         }
-        if (made) level_from_window<T, VS, DX, MODE, LW>(WA[l - 2], WB[l - 2], N, a, lane, r0, et, walls, flux, fown, q, out);
+        if (made)
+            level_from_window<T, VS, DX, MODE, LW, XF>(WA[l - 2], WB[l - 2], N, a, lane, r0, et, walls, flux, fown, q, out);
         // level K's columns of the made steps are exactly the sweep's outputs [xa, xb)
         bool keep = owner;
         if constexpr ((MODE & MODE_SKIP) != 0)
@@ -952,7 +956,9 @@ __device__ __forceinline__ void sweepk_iter(const Sweep2Args<T>& a, int i, int n
 // NOFLUX: the sweep holds no flux column (the waves of all sweeps but one): the walk is built without
 // the per-level flux test and its branch (round 6: the test's spilled SGPRs cost a v_readlane and a
 // compare per level and cell of every wave)
-template <typename T, int VS, int MODE, int K, bool SLAB, bool REV, bool WL, bool NOFLUX = false>
+// XF: the collides built for a body force along x only (relax_cells; sweepk_kernel gives it to its
+// VS-cell walks, the one-cell wall walks keep relax_cell)
+template <typename T, int VS, int MODE, int K, bool SLAB, bool REV, bool WL, bool NOFLUX = false, bool XF = false>
 __device__ __forceinline__ double sweepk_walk(const Sweep2Args<T>& a, int xa, int xb, int row0, unsigned off,
                                               int lane, int r0, int et, bool owner, bool bot_, bool top_, T* lw) {
     const bool walls = WL, bot = WL && bot_, top = WL && top_;
@@ -1027,8 +1033,8 @@ __device__ __forceinline__ double sweepk_walk(const Sweep2Args<T>& a, int xa, in
 #pragma clang loop unroll(disable)
         for (;;) {
             for (; i < ge; ++i)
-                sweepk_iter<T, VS, MODE, K, SLAB, REV, LW, LW>(a, i, nl1, x0, xa, xb, row0, off, lane, r0, et, owner, bot, top,
-                                                               walls, WA, WB, cur, q, bo, rc, true, fx, fown, sp, lw, cp);
+                sweepk_iter<T, VS, MODE, K, SLAB, REV, LW, LW, false, XF>(a, i, nl1, x0, xa, xb, row0, off, lane, r0, et, owner, bot, top,
+                                                                          walls, WA, WB, cur, q, bo, rc, true, fx, fown, sp, lw, cp);
             if (i >= nl1) break;
             if (i > fx) {  // (before the first flux step q is zero)
                 const double qs = wave_sum(q);
@@ -1037,7 +1043,7 @@ __device__ __forceinline__ double sweepk_walk(const Sweep2Args<T>& a, int xa, in
             q = 0.;
             const int se = i >= fx + K ? nl1 : min(max(fx, i), nl1);
             for (; i < se; ++i)
-                sweepk_iter<T, VS, MODE, K, SLAB, REV, LW, LW, true>(a, i, nl1, x0, xa, xb, row0, off, lane, r0, et, owner, bot,
+                sweepk_iter<T, VS, MODE, K, SLAB, REV, LW, LW, true, XF>(a, i, nl1, x0, xa, xb, row0, off, lane, r0, et, owner, bot,
                                                                      top, walls, WA, WB, cur, q, bo, rc, false, fx, fown, sp, lw,
                                                                      cp);
             if (i >= nl1) break;
@@ -1045,7 +1051,7 @@ __device__ __forceinline__ double sweepk_walk(const Sweep2Args<T>& a, int xa, in
         }
     } else {
         for (int i = 0; i < nl1; ++i)
-            sweepk_iter<T, VS, MODE, K, SLAB, REV, LW, LW>(a, i, nl1, x0, xa, xb, row0, off, lane, r0, et, owner, bot, top, walls,
+            sweepk_iter<T, VS, MODE, K, SLAB, REV, LW, LW, false, XF>(a, i, nl1, x0, xa, xb, row0, off, lane, r0, et, owner, bot, top, walls,
                                                            WA, WB, cur, q, bo, rc, fin, fi, fown, sp, lw, cp);
     }
     return q;
@@ -1131,9 +1137,21 @@ __host__ __device__ inline void balanced_range(int cb, int ce, int s, int nsw, i
     xb = cb + (int)((s + 1) * n / nsw);
 }
 
+// The builds of deep_builds that also exist with the collide for a body force along x only (XF, the
+// builds' second axis): the ones whose inner walks collide through relax_cells / the packed relax_dev
+// and that the context's defaults select: f64 785 lone and SLAB, f32 593 (lone only).
+template <typename T, int VS, int MODE, bool SLAB>
+constexpr bool has_force_build() {
+    constexpr int WIN = 1 | MODE_SPLIT | MODE_LDSWIN;
+    return VS == 2 && (sizeof(T) == 8 ? MODE == (WIN | MODE_PRESHIFT) : MODE == (WIN | MODE_PACK) && !SLAB);
+}
+
 // G ghost lanes at each wave edge (G * VS >= K - 1 rows)
-template <typename T, int VS, int MODE, int K, bool SLAB, int WPE>
+// XF: the inner chunks' walks collide with the build for F_y = 0 (launch_sweepk_mode takes it from the
+// launch's force constants); the one-cell wall walks keep relax_cell
+template <typename T, int VS, int MODE, int K, bool SLAB, int WPE, bool XF>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void sweepk_kernel(Sweep2Args<T> a) {
+    static_assert(!XF || has_force_build<T, VS, MODE, SLAB>(), "no x-only force build of this kernel");
     constexpr int G = ghost_lanes<K, VS>();
     constexpr int OWN = 64 - 2 * G;  // owned lanes per wave
     const int lane = threadIdx.x & 63;
@@ -1207,18 +1225,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
         if constexpr (SLAB) {
             if (wt) {
                 constexpr int MW = MODE | MODE_WT_STORE;
-                q = rev ? sweepk_walk<T, VS, MW, K, SLAB, true, false>(a, xa, xb, row0, off, lane, r0, et, owner, false, false, lw)
-                        : sweepk_walk<T, VS, MW, K, SLAB, false, false>(a, xa, xb, row0, off, lane, r0, et, owner, false, false, lw);
+                q = rev ? sweepk_walk<T, VS, MW, K, SLAB, true, false, false, XF>(a, xa, xb, row0, off, lane, r0, et, owner, false,
+                                                                                  false, lw)
+                        : sweepk_walk<T, VS, MW, K, SLAB, false, false, false, XF>(a, xa, xb, row0, off, lane, r0, et, owner, false,
+                                                                                   false, lw);
                 goto walked;
             }
         }
         // (f32: the flux-free walk spills 20 B; the walks in step ranges have no flux-free build)
         if (step_ranges<T, VS, MODE, false, SLAB>() || sizeof(T) == 4 || (a.flux_col >= 0 && a.flux_col >= xa && a.flux_col < xb))
-            q = rev ? sweepk_walk<T, VS, MODE, K, SLAB, true, false>(a, xa, xb, row0, off, lane, r0, et, owner, false, false, lw)
-                    : sweepk_walk<T, VS, MODE, K, SLAB, false, false>(a, xa, xb, row0, off, lane, r0, et, owner, false, false, lw);
+            q = rev ? sweepk_walk<T, VS, MODE, K, SLAB, true, false, false, XF>(a, xa, xb, row0, off, lane, r0, et, owner, false,
+                                                                                false, lw)
+                    : sweepk_walk<T, VS, MODE, K, SLAB, false, false, false, XF>(a, xa, xb, row0, off, lane, r0, et, owner, false,
+                                                                                 false, lw);
         else
-            q = rev ? sweepk_walk<T, VS, MODE, K, SLAB, true, false, true>(a, xa, xb, row0, off, lane, r0, et, owner, false, false, lw)
-                    : sweepk_walk<T, VS, MODE, K, SLAB, false, false, true>(a, xa, xb, row0, off, lane, r0, et, owner, false, false, lw);
+            q = rev ? sweepk_walk<T, VS, MODE, K, SLAB, true, false, true, XF>(a, xa, xb, row0, off, lane, r0, et, owner, false,
+                                                                               false, lw)
+                    : sweepk_walk<T, VS, MODE, K, SLAB, false, false, true, XF>(a, xa, xb, row0, off, lane, r0, et, owner, false,
+                                                                                false, lw);
     } else {
         const int cs = ch * (OWN * VS);
         const int row0 = cs - G * VS;
@@ -1245,32 +1269,41 @@ walked:
 }
 
 // Waves of one instantiation resident per CU (256-thread workgroups), and on `cus` CUs (0: all).
-template <typename T, int VS, int MODE, int K, bool SLAB, int WPE>
+template <typename T, int VS, int MODE, int K, bool SLAB, int WPE, bool XF = false>
 static long waves_per_cu() {
     static long cached = 0;
     if (cached) return cached;
     int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, sweepk_kernel<T, VS, MODE, K, SLAB, WPE>, 256, 0) !=
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, sweepk_kernel<T, VS, MODE, K, SLAB, WPE, XF>, 256, 0) !=
             hipSuccess ||
         nb <= 0)
         return 0;
     cached = (long)nb * 4;
     return cached;
 }
-template <typename T, int VS, int MODE, int K, bool SLAB, int WPE>
+template <typename T, int VS, int MODE, int K, bool SLAB, int WPE, bool XF = false>
 static long resident_waves(int cus) {
     int dev = 0, ncu = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
         return 0;
-    return waves_per_cu<T, VS, MODE, K, SLAB, WPE>() * (cus > 0 ? std::min(cus, ncu) : ncu);
+    return waves_per_cu<T, VS, MODE, K, SLAB, WPE, XF>() * (cus > 0 ? std::min(cus, ncu) : ncu);
 }
 
 // One build's launch: sweeps and waves sized by deep_plan.h from this build's resident waves
-template <typename T, int VS, int MODE, int K, bool SLAB, int WPE>
+// (XF: the occupancy and register-count caches below are per instantiation, so kinfo names the kernel
+// that runs)
+template <typename T, int VS, int MODE, int K, bool SLAB, int WPE, bool XF = false>
 static hipError_t launch_sweepk_mode(Sweep2Args<T> b, hipStream_t s, hipEvent_t stop, hipEvent_t start) {
     constexpr bool SPLIT = (MODE & MODE_SPLIT) != 0;
-    const long slots = b.col_step <= 0 ? resident_waves<T, VS, MODE, K, SLAB, WPE>(b.cus) : 0;
+    if constexpr (!XF && has_force_build<T, VS, MODE, SLAB>()) {
+        // the collide for a body force along x only, where the launch's constants allow it
+        // (IBLB_DEEP_FORCE=general, build.general_force: the general one whatever the force)
+        const auto& f = kbody<typename Calc<T>::R>(b.k);
+        if (!b.build.general_force && deep_force_x_only(f.Fx, f.Fy))
+            return launch_sweepk_mode<T, VS, MODE, K, SLAB, WPE, true>(b, s, stop, start);
+    }
+    const long slots = b.col_step <= 0 ? resident_waves<T, VS, MODE, K, SLAB, WPE, XF>(b.cus) : 0;
     const DeepSweeps p =
         deep_sweeps(SPLIT, VS, b.col_begin, b.col_end, b.col_step, b.W, b.nsweep, b.nch, b.wall_ch0, slots);
     b.nsweep = p.nsweep;
@@ -1282,21 +1315,22 @@ static hipError_t launch_sweepk_mode(Sweep2Args<T> b, hipStream_t s, hipEvent_t 
         static int vgprs = -1;
         if (vgprs < 0) {
             hipFuncAttributes fa{};
-            vgprs = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&sweepk_kernel<T, VS, MODE, K, SLAB, WPE>)) ==
+            vgprs = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&sweepk_kernel<T, VS, MODE, K, SLAB, WPE, XF>)) ==
                             hipSuccess
                         ? fa.numRegs
                         : 0;
         }
         b.kinfo[0] = MODE;
         b.kinfo[1] = VS;
-        b.kinfo[2] = (int)(waves_per_cu<T, VS, MODE, K, SLAB, WPE>() / 4);
+        b.kinfo[2] = (int)(waves_per_cu<T, VS, MODE, K, SLAB, WPE, XF>() / 4);
         b.kinfo[3] = vgprs;
+        b.kinfo[4] = XF ? 1 : 0;
     }
     const unsigned blocks = (unsigned)((p.waves + 3) / 4);
     if (stop || start)  // the events ride on the kernel's own signals: no marker packets around it
-        hipExtLaunchKernelGGL(sweepk_kernel<T, VS, MODE, K, SLAB, WPE>, dim3(blocks), dim3(256), 0, s, start, stop, 0, b);
+        hipExtLaunchKernelGGL(sweepk_kernel<T, VS, MODE, K, SLAB, WPE, XF>, dim3(blocks), dim3(256), 0, s, start, stop, 0, b);
     else
-        sweepk_kernel<T, VS, MODE, K, SLAB, WPE><<<blocks, 256, 0, s>>>(b);
+        sweepk_kernel<T, VS, MODE, K, SLAB, WPE, XF><<<blocks, 256, 0, s>>>(b);
     return hipGetLastError();
 }
 

@@ -526,6 +526,11 @@ class Lattice:
         self._check(self._lib.iblb_get_timing_ex(self._h, C.byref(t), C.sizeof(t), 1 if reset else 0))
         return {k: getattr(t, k) for k, _ in L.Timing._fields_}
 
+    def deep_force_build(self) -> int:
+        """The collide build of the last deep launch (include/iblb.h iblb_deep_force_build): 1 the one
+        for a body force along x only, 0 the general one, -1 no deep launch yet."""
+        return int(self._lib.iblb_deep_force_build(self._h))
+
     @property
     def stream(self) -> int:
         s = C.c_void_p()

@@ -505,6 +505,11 @@ int iblb_get_timing(iblb_ctx* ctx, iblb_timing* t, int reset);
  * caller was built with: an older, shorter iblb_timing gets its own fields only).  iblb_get_timing
  * writes sizeof(iblb_timing) of THIS header. */
 int iblb_get_timing_ex(iblb_ctx* ctx, iblb_timing* t, unsigned long bytes, int reset);
+/* The collide build of the context's last deep launch (the one iblb_timing's deep_mode ... deep_vgprs
+ * name): 1 the build for a body force along x only (F_y = 0: the same populations bit for bit, fewer
+ * operations), 0 the general one (F_y != 0, a build without the x-only variant, or IBLB_DEEP_FORCE=general),
+ * -1 no deep launch yet (or ctx NULL).  No struct changed for it: the ABI version stays. */
+int iblb_deep_force_build(const iblb_ctx* ctx);
 /* The stream the context launches on (hipStream_t), for callers that add work. */
 int iblb_get_stream(iblb_ctx* ctx, void** stream);
 /* Block until all work of the context is done. */
