@@ -103,6 +103,19 @@ class Scalar(C.Structure):
     _fields_ = [("tau", C.c_double), ("stride", C.c_int), ("wall_kind", C.c_int * 2), ("wall_value", C.c_double * 2)]
 
 
+class ScalarSource(C.Structure):
+    """struct iblb_scalar_source (include/iblb.h)."""
+    _fields_ = [("source", C.c_void_p), ("decay", C.c_double), ("wall_flux", C.c_void_p * 2),
+                ("wall_value", C.c_void_p * 2)]
+
+
+# the `present` bits of iblb_scalar_source_info
+SCALAR_SOURCE_SET = 1
+SCALAR_SOURCE_FIELD = 2
+SCALAR_SOURCE_WALL_FLUX = (4, 8)
+SCALAR_SOURCE_WALL_VALUE = (16, 32)
+
+
 class FieldStats(C.Structure):
     """struct iblb_field_stats (include/iblb.h)."""
     _fields_ = [
@@ -165,6 +178,9 @@ _SIGS = {
     "iblb_get_scalar_populations": ([_vp, _vp], C.c_int),
     "iblb_scalar_info": ([_vp, C.POINTER(Scalar), C.POINTER(C.c_longlong)], C.c_int),
     "iblb_get_scalar_wall_flux": ([_vp, _vp, _vp], C.c_int),
+    "iblb_set_scalar_source": ([_vp, C.POINTER(ScalarSource)], C.c_int),
+    "iblb_scalar_source_info": ([_vp, C.POINTER(C.c_double), C.POINTER(C.c_uint)], C.c_int),
+    "iblb_get_scalar_source": ([_vp, _vp], C.c_int),
     "iblb_set_profiling": ([_vp, C.c_int], C.c_int),
     "iblb_get_timing": ([_vp, C.POINTER(Timing), C.c_int], C.c_int),
     "iblb_get_timing_ex": ([_vp, C.POINTER(Timing), C.c_ulong, C.c_int], C.c_int),

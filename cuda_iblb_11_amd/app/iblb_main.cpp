@@ -42,6 +42,10 @@
 // Checkpoints hold no scalar: a restarted run seeds it again.  With IBLB_STATS=1 as well, one more iblb_reduce_fields
 // call (IBLB_FIELD_C, _CUX, _CUY over the whole lattice) appends one line per output iteration to <..>-cstats.dat beside
 // the flux file (lattice units, %.17g):  it  sum(C)  sum(C^2)  min C  max C  sum(C u_x)  sum(C u_y)
+// IBLB_SCALAR_SOURCE=flux[,decay] (needs IBLB_SCALAR) gives that scalar a source (iblb_set_scalar_source): the amount
+// `flux` of C enters every column through the bottom wall per substep, and C decays everywhere at the first-order
+// rate `decay` per substep (default 0); both finite, decay >= 0.  Everything else about IBLB_SCALAR stays as it is;
+// with both set, sum(C) in <..>-cstats.dat tends to flux XDIM / decay.
 #include <sys/stat.h>
 #include <sys/time.h>
 #include <unistd.h>
@@ -288,6 +292,37 @@ int main(int argc, char* argv[]) {
         }
     }
 
+    // the scalar's source (extension): a uniform influx through the bottom wall and a bulk decay
+    bool sc_source = false;
+    double sc_flux = 0., sc_decay = 0.;
+    if (const char* ss = getenv("IBLB_SCALAR_SOURCE"); ss && *ss) {
+        // one or two finite numbers separated by a comma, nothing else; the second >= 0
+        double* const dst[2] = {&sc_flux, &sc_decay};
+        const char* p = ss;
+        bool ok = true;
+        for (int n = 0; ok; ++n) {
+            char* end = nullptr;
+            errno = 0;
+            const double v = strtod(p, &end);
+            ok = n < 2 && ((*p >= '0' && *p <= '9') || *p == '.' || *p == '-' || *p == '+') && end != p && errno == 0 &&
+                 std::isfinite(v) && (n == 0 || v >= 0.) && (*end == ',' || *end == 0);
+            if (!ok) break;
+            *dst[n] = v;
+            if (*end == 0) break;
+            p = end + 1;
+        }
+        if (!ok) {
+            if (lead)
+                cerr << "IBLB_SCALAR_SOURCE must be flux[,decay], both finite and decay >= 0, got " << ss << endl;
+            return 2;
+        }
+        if (!(sc_tau > 0.)) {
+            if (lead) cerr << "IBLB_SCALAR_SOURCE needs IBLB_SCALAR: there is no scalar to feed" << endl;
+            return 2;
+        }
+        sc_source = true;
+    }
+
     const double dx = 1. / LENGTH;
     const double dt = 1. / (T);
     const double SPEED = 0.8 * 1000 / T;
@@ -389,6 +424,11 @@ int main(int argc, char* argv[]) {
         for (int j = 0; j < size; j++) c0[j] = (unsigned int)j / XDIM < YDIM / 2 ? 1. : 0.;
         iblb_scalar sk{sc_tau, sc_stride, {IBLB_SCALAR_WALL_NOFLUX, IBLB_SCALAR_WALL_NOFLUX}, {0., 0.}};
         if ((rc = iblb_set_scalar(ctx, &sk, c0.data(), nullptr))) return die(ctx, rc, "iblb_set_scalar");
+        if (sc_source) {
+            const std::vector<double> influx((size_t)XDIM, sc_flux);
+            const iblb_scalar_source src{nullptr, sc_decay, {influx.data(), nullptr}, {nullptr, nullptr}};
+            if ((rc = iblb_set_scalar_source(ctx, &src))) return die(ctx, rc, "iblb_set_scalar_source");
+        }
     }
 
     //----------------------------------------DEFINE DIRECTORIES---------------------------------- (main.cu:589-631)

@@ -219,6 +219,13 @@ struct iblb_ctx {
     int sc_cur = 0;
     iblb_scalar sc_cfg{};   // as given (stride also in sc_ev)
     iblbh::Periodic sc_ev;  // count: events run since iblb_set_scalar
+    // the scalar's source (iblb_set_scalar_source).  sc_src_present == 0: none.  sc_src_field: one plane in the
+    // scalar's layout; sc_src_walls: [4 * ncol], wall_flux[0], wall_flux[1], wall_value[0], wall_value[1]; a NULL
+    // array of the call is held as zeros (wall_value: as the uniform value).  Lives and dies with the scalar.
+    double* sc_src_field = nullptr;
+    double* sc_src_walls = nullptr;
+    double sc_src_decay = 0.0;
+    unsigned sc_src_present = 0;  // the `present` bits of iblb_scalar_source_info
     // state machine
     int phase = iblbh::PH_EMPTY;
     long long t = 0;

@@ -3,13 +3,24 @@
 // (iblb_set_average) and the passive scalar (iblb_set_scalar), each on a Periodic schedule; iblb_step asks
 // next_event where to cut a call and run_events to run what is due there.  Built from the read scaffold of
 // ctx.h like the readers.
+#include <algorithm>
 #include <cmath>
+#include <vector>
 
 #include "ctx.h"
 
 namespace iblbh {
 
+static void scalar_source_free(iblb_ctx* c) {
+    for (void* p : {(void*)c->sc_src_field, (void*)c->sc_src_walls})
+        if (p) (void)hipFree(p);
+    c->sc_src_field = c->sc_src_walls = nullptr;
+    c->sc_src_decay = 0.0;
+    c->sc_src_present = 0;
+}
+
 void scalar_free(iblb_ctx* c) {
+    scalar_source_free(c);  // the source belongs to the scalar it was set on
     if (c->sc_alloc) (void)hipFree(c->sc_alloc);
     c->sc_alloc = c->sc_g[0] = c->sc_g[1] = c->sc_uv = nullptr;
     c->sc_cur = 0;
@@ -23,6 +34,11 @@ static ScalarGeom scalar_geom(const iblb_ctx* c) {
 
 static ScalarRule scalar_rule(const iblb_scalar& k) {
     return ScalarRule{1.0 / k.tau, {k.wall_kind[0], k.wall_kind[1]}, {k.wall_value[0], k.wall_value[1]}};
+}
+
+// nullptr members without a source: the launchers then run the builds without one
+static ScalarSource scalar_source(const iblb_ctx* c) {
+    return ScalarSource{c->sc_src_field, c->sc_src_walls, c->sc_src_decay};
 }
 
 void tracers_free(iblb_ctx* c) {
@@ -84,7 +100,8 @@ static int average_update(iblb_ctx* c) {
 
 // One event of the scalar on the context's stream: the state prepared as for a reader (the band streams
 // joined, the owed IB force evaluated), then `stride` substeps with the velocity of this state: the first
-// evaluates it from the fluid populations and leaves it in the scratch, the others read the scratch.
+// evaluates it from the fluid populations and leaves it in the scratch, the others read the scratch.  With a source
+// (iblb_set_scalar_source) every substep runs the SOURCE build, without one the build that has none.
 static int scalar_update(iblb_ctx* c) {
     if (!single_slab(c))  // the context joined a group after iblb_set_scalar: its lattice is the whole lattice's
         return fail(c, IBLB_ERR_UNSUPPORTED, "scalar: a lone slab only; remove it before joining a group");
@@ -93,12 +110,13 @@ static int scalar_update(iblb_ctx* c) {
     const FieldsArgs a = point_args(c, IBLB_FIELD_UX | IBLB_FIELD_UY);
     const ScalarGeom S = scalar_geom(c);
     const ScalarRule R = scalar_rule(c->sc_cfg);
+    const ScalarSource Q = scalar_source(c);
     HIP_TRY(c, with_state(c, [&](auto* g, auto H) {
-        return launch_scalar_first(g, c->L, H, a, S, R, c->sc_g[c->sc_cur], c->sc_g[c->sc_cur ^ 1], c->sc_uv, c->stream);
+        return launch_scalar_first(g, c->L, H, a, S, R, Q, c->sc_g[c->sc_cur], c->sc_g[c->sc_cur ^ 1], c->sc_uv, c->stream);
     }));
     c->sc_cur ^= 1;
     for (int k = 1; k < c->sc_ev.stride; ++k) {
-        HIP_TRY(c, launch_scalar_next(S, R, c->sc_g[c->sc_cur], c->sc_g[c->sc_cur ^ 1], c->sc_uv, c->stream));
+        HIP_TRY(c, launch_scalar_next(S, R, Q, c->sc_g[c->sc_cur], c->sc_g[c->sc_cur ^ 1], c->sc_uv, c->stream));
         c->sc_cur ^= 1;
     }
     c->sc_ev.advance();
@@ -379,7 +397,8 @@ int iblb_get_scalar_wall_flux(iblb_ctx* c, double* bottom, double* top) {
     const size_t nb = (size_t)c->ncol * sizeof(double);
     DevBuf d;
     HIP_TRY(c, hipMalloc(&d.p, 2 * nb));
-    HIP_TRY(c, launch_scalar_wall_flux(c->sc_g[c->sc_cur], scalar_geom(c), scalar_rule(c->sc_cfg), (double*)d.p, c->stream));
+    HIP_TRY(c, launch_scalar_wall_flux(c->sc_g[c->sc_cur], scalar_geom(c), scalar_rule(c->sc_cfg), scalar_source(c),
+                                       (double*)d.p, c->stream));
     return read_back(c, {{bottom, d.p, nb}, {top, (double*)d.p + c->ncol, nb}});
 }
 
@@ -388,6 +407,96 @@ int iblb_scalar_info(iblb_ctx* c, iblb_scalar* cfg, long long* updates) {
     if (cfg) *cfg = c->sc_cfg;
     if (updates) *updates = c->sc_ev.count;
     return IBLB_OK;
+}
+
+// ---- the scalar's source ------------------------------------------------------------------------------
+static bool all_finite(const double* a, size_t n) {
+    for (size_t j = 0; j < n; ++j)
+        if (!std::isfinite(a[j])) return false;
+    return true;
+}
+
+int iblb_set_scalar_source(iblb_ctx* c, const iblb_scalar_source* src) {
+    if (!c) return IBLB_ERR_ARG;
+    if (!c->sc_alloc)
+        return fail(c, IBLB_ERR_STATE, single_slab(c) ? "iblb_set_scalar_source: no scalar is set (iblb_set_scalar)"
+                                                      : "iblb_set_scalar_source: a slab of a group holds no scalar");
+    const size_t N = (size_t)c->ncol * c->ny, ncol = (size_t)c->ncol;
+    if (src) {
+        if (!std::isfinite(src->decay) || src->decay < 0.0) return fail(c, IBLB_ERR_ARG, "decay must be finite and >= 0");
+        if (src->source && !all_finite(src->source, N)) return fail(c, IBLB_ERR_ARG, "source holds a non-finite entry");
+        for (int k = 0; k < 2; ++k) {
+            const bool value = c->sc_cfg.wall_kind[k] == IBLB_SCALAR_WALL_VALUE;
+            if (src->wall_flux[k] && value)
+                return fail(c, IBLB_ERR_ARG, "wall_flux is given for a wall of kind IBLB_SCALAR_WALL_VALUE");
+            if (src->wall_value[k] && !value)
+                return fail(c, IBLB_ERR_ARG, "wall_value is given for a wall of kind IBLB_SCALAR_WALL_NOFLUX");
+            if (src->wall_flux[k] && !all_finite(src->wall_flux[k], ncol))
+                return fail(c, IBLB_ERR_ARG, "wall_flux holds a non-finite entry");
+            if (src->wall_value[k] && !all_finite(src->wall_value[k], ncol))
+                return fail(c, IBLB_ERR_ARG, "wall_value holds a non-finite entry");
+        }
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (!src) {
+        scalar_source_free(c);
+        return IBLB_OK;
+    }
+    // the four wall arrays side by side; what the call leaves NULL is held as the value the rule then uses
+    std::vector<double> walls(4 * ncol, 0.0);
+    unsigned present = 1u | (src->source ? 2u : 0u);
+    for (int k = 0; k < 2; ++k) {
+        if (src->wall_flux[k]) {
+            std::copy(src->wall_flux[k], src->wall_flux[k] + ncol, walls.begin() + (size_t)k * ncol);
+            present |= 4u << k;
+        }
+        if (src->wall_value[k]) {
+            std::copy(src->wall_value[k], src->wall_value[k] + ncol, walls.begin() + (size_t)(2 + k) * ncol);
+            present |= 16u << k;
+        } else if (c->sc_cfg.wall_kind[k] == IBLB_SCALAR_WALL_VALUE) {
+            std::fill_n(walls.begin() + (size_t)(2 + k) * ncol, ncol, c->sc_cfg.wall_value[k]);
+        }
+    }
+    // the new buffers first: a failed allocation leaves the previous source as it was
+    const ScalarGeom S = scalar_geom(c);
+    DevBuf df, dw, in;
+    HIP_TRY(c, hipMalloc(&df.p, (size_t)S.plane * sizeof(double)));
+    HIP_TRY(c, hipMalloc(&dw.p, 4 * ncol * sizeof(double)));
+    HIP_TRY(c, hipMemsetAsync(df.p, 0, (size_t)S.plane * sizeof(double), c->stream));
+    if (src->source) {
+        HIP_TRY(c, hipMalloc(&in.p, N * sizeof(double)));
+        HIP_TRY(c, hipMemcpyAsync(in.p, src->source, N * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, launch_scalar_in((const double*)in.p, S, 1, (double*)df.p, c->stream));
+    }
+    HIP_TRY(c, hipMemcpyAsync(dw.p, walls.data(), 4 * ncol * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    scalar_source_free(c);
+    c->sc_src_field = (double*)df.p;
+    c->sc_src_walls = (double*)dw.p;
+    df.p = dw.p = nullptr;
+    c->sc_src_decay = src->decay;
+    c->sc_src_present = present;
+    return IBLB_OK;
+}
+
+int iblb_scalar_source_info(iblb_ctx* c, double* decay, unsigned* present) {
+    if (!c) return IBLB_ERR_ARG;
+    if (decay) *decay = c->sc_src_decay;
+    if (present) *present = c->sc_src_present;
+    return IBLB_OK;
+}
+
+int iblb_get_scalar_source(iblb_ctx* c, double* source) {
+    if (!c) return IBLB_ERR_ARG;
+    if (!c->sc_src_present) return fail(c, IBLB_ERR_STATE, "iblb_get_scalar_source: no source is set");
+    if (!source) return fail(c, IBLB_ERR_ARG, "source is NULL");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t nb = (size_t)c->ncol * c->ny * sizeof(double);
+    DevBuf d;
+    HIP_TRY(c, hipMalloc(&d.p, nb));
+    HIP_TRY(c, launch_scalar_plane_out(c->sc_src_field, scalar_geom(c), (double*)d.p, c->stream));
+    return read_back(c, source, d.p, nb);
 }
 
 }  // extern "C"

@@ -274,13 +274,21 @@ struct ScalarRule {
     int wall_kind[2];      // IBLB_SCALAR_WALL_*: below row 0, above row ny - 1
     double wall_value[2];
 };
+// The scalar's source (include/iblb.h iblb_set_scalar_source).  field == nullptr: none, and every launch below runs
+// the build without it.  Otherwise all three members are set: a NULL array of the ABI is a device array of zeros
+// (wall_value: of the uniform value), so that the kernels have no per-pointer branch.
+struct ScalarSource {
+    const double* field;  // one plane [x * rows + y]: s(x, y)
+    const double* walls;  // [4 * ncol]: wall_flux[0], wall_flux[1], wall_value[0], wall_value[1], [ncol] each
+    double decay;
+};
 // One substep src -> dst (distinct buffers).  first: the velocity from the fluid state by cell_state of
 // field_eval.h (of FieldsArgs the window members are unused), also left in uv; next: the velocity read from uv.
 template <typename T>
 hipError_t launch_scalar_first(const T* f, Layout L, Halo<T> H, const FieldsArgs& a, ScalarGeom S, ScalarRule R,
-                               const double* src, double* dst, double* uv, hipStream_t s);
-hipError_t launch_scalar_next(ScalarGeom S, ScalarRule R, const double* src, double* dst, const double* uv,
-                              hipStream_t s);
+                               ScalarSource Q, const double* src, double* dst, double* uv, hipStream_t s);
+hipError_t launch_scalar_next(ScalarGeom S, ScalarRule R, ScalarSource Q, const double* src, double* dst,
+                              const double* uv, hipStream_t s);
 // dst's five planes = the equilibrium of C = c[x * rows + y] at the fluid state's velocity; c may be dst's plane 0.
 template <typename T>
 hipError_t launch_scalar_init(const T* f, Layout L, Halo<T> H, const FieldsArgs& a, ScalarGeom S, const double* c,
@@ -293,8 +301,12 @@ hipError_t launch_scalar_populations_out(const double* dev, ScalarGeom S, double
 hipError_t launch_scalar_out(const double* dev, ScalarGeom S, int x0, int y0, int nxw, int nyw, int sx, int sy,
                              double* out, hipStream_t s);
 // The wall flux of the last substep (include/iblb.h iblb_get_scalar_wall_flux): out[x] through the wall below row 0,
-// out[ncol + x] through the wall above row ny - 1.
-hipError_t launch_scalar_wall_flux(const double* dev, ScalarGeom S, ScalarRule R, double* out, hipStream_t s);
+// out[ncol + x] through the wall above row ny - 1.  With a source: its wall_flux at a no-flux wall, its wall_value
+// in the expression of a _VALUE wall.
+hipError_t launch_scalar_wall_flux(const double* dev, ScalarGeom S, ScalarRule R, ScalarSource Q, double* out,
+                                   hipStream_t s);
+// One plane out in the reference layout: out[y * ncol + x] = dev[x * rows + y] (iblb_get_scalar_source).
+hipError_t launch_scalar_plane_out(const double* dev, ScalarGeom S, double* out, hipStream_t s);
 
 // q(u^t) of the current state for the flux column (added to *out).
 template <typename T>

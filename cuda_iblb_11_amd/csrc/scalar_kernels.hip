@@ -15,6 +15,11 @@
 // The first substep of an event evaluates (ux, uy) with cell_state of field_eval.h, so its bits are those of
 // iblb_get_fields, and leaves them in the scratch; the later substeps read the scratch, not the nine populations.
 // Contraction is off everywhere: one rounding per operation, as the rule of include/iblb.h states it.
+// With a source (iblb_set_scalar_source) the SOURCE builds of the substep run: one more plane loaded, s(x, y) in the
+// same layout, 104 bytes per cell; the lanes of rows 0 and ny - 1 also load their column's wall entry from one
+// 4 * ncol array (the flux or the value, by the wall's kind).  Every term of the rule is evaluated: what the call
+// left NULL is an array of zeros (or of the uniform wall value) on the device.  Without a source the builds
+// without SOURCE run: the kernels as they were.
 //
 // The transposes between the ABI's layouts ([y * nx + x]) and the device's go through an LDS tile so that both
 // sides coalesce.
@@ -28,16 +33,26 @@ constexpr int TILE = 32;  // transposes: TILE x TILE elements per workgroup of T
 constexpr double SW0 = 1.0 / 3.0, SW1 = 1.0 / 6.0;
 
 // One cell of a substep: g[5] of cell (x, y) relaxed towards the equilibrium at (ux, uy) and pushed into dst.
+// SOURCE: the rule of iblb_set_scalar_source.  sv = s(x, y) of the lane's cell; the lanes of rows 0 and ny - 1 load
+// their column's one wall entry (the flux or the value, by the wall's kind) from Q.walls.
+template <bool SOURCE>
 __device__ __forceinline__ void scalar_push(const double g[5], double ux, double uy, const ScalarGeom& S,
-                                            const ScalarRule& R, int x, int y, double* __restrict__ dst) {
+                                            const ScalarRule& R, const ScalarSource& Q, double sv, int x, int y,
+                                            double* __restrict__ dst) {
 #pragma clang fp contract(off)
     const double C = (((g[0] + g[1]) + g[2]) + g[3]) + g[4];
     const double a[5] = {0.0, ux, -ux, uy, -uy};
     double p[5];
+    double r = 0.0;
+    if constexpr (SOURCE) {
+        const double m = Q.decay * C;
+        r = sv - m;
+    }
 #pragma unroll
     for (int i = 0; i < 5; ++i) {
         const double geq = ((i == 0 ? SW0 : SW1) * C) * (1.0 + 3.0 * a[i]);
         p[i] = g[i] - R.omega * (g[i] - geq);
+        if constexpr (SOURCE) p[i] = p[i] + (i == 0 ? SW0 : SW1) * r;
     }
     const long o = (long)x * S.rows + y;
     const long oxp = (long)(x + 1 < S.ncol ? x + 1 : 0) * S.rows + y;
@@ -45,38 +60,59 @@ __device__ __forceinline__ void scalar_push(const double g[5], double ux, double
     dst[o] = p[0];
     dst[S.plane + oxp] = p[1];
     dst[2 * S.plane + oxm] = p[2];
-    if (y + 1 < S.ny) dst[3 * S.plane + o + 1] = p[3];
-    else dst[4 * S.plane + o] = R.wall_kind[1] == IBLB_SCALAR_WALL_VALUE ? (2.0 * SW1) * R.wall_value[1] - p[3] : p[3];
-    if (y > 0) dst[4 * S.plane + o - 1] = p[4];
-    else dst[3 * S.plane + o] = R.wall_kind[0] == IBLB_SCALAR_WALL_VALUE ? (2.0 * SW1) * R.wall_value[0] - p[4] : p[4];
+    if constexpr (SOURCE) {
+        if (y + 1 < S.ny) dst[3 * S.plane + o + 1] = p[3];
+        else {
+            const bool value = R.wall_kind[1] == IBLB_SCALAR_WALL_VALUE;
+            const double e = Q.walls[(long)(value ? 3 : 1) * S.ncol + x];
+            dst[4 * S.plane + o] = value ? (2.0 * SW1) * e - p[3] : p[3] + e;
+        }
+        if (y > 0) dst[4 * S.plane + o - 1] = p[4];
+        else {
+            const bool value = R.wall_kind[0] == IBLB_SCALAR_WALL_VALUE;
+            const double e = Q.walls[(long)(value ? 2 : 0) * S.ncol + x];
+            dst[3 * S.plane + o] = value ? (2.0 * SW1) * e - p[4] : p[4] + e;
+        }
+    } else {
+        if (y + 1 < S.ny) dst[3 * S.plane + o + 1] = p[3];
+        else dst[4 * S.plane + o] = R.wall_kind[1] == IBLB_SCALAR_WALL_VALUE ? (2.0 * SW1) * R.wall_value[1] - p[3] : p[3];
+        if (y > 0) dst[4 * S.plane + o - 1] = p[4];
+        else dst[3 * S.plane + o] = R.wall_kind[0] == IBLB_SCALAR_WALL_VALUE ? (2.0 * SW1) * R.wall_value[0] - p[4] : p[4];
+    }
 }
 
-// grid: (ncol, ceil(ny / 256)); one lane per cell
-template <typename T>
+// grid: (ncol, ceil(ny / 256)); one lane per cell.  The SOURCE builds load one more plane, Q.field; the others
+// never touch Q.
+template <typename T, bool SOURCE>
 __global__ __launch_bounds__(256) void scalar_first_kernel(const T* __restrict__ f, Layout L, Halo<T> H, FieldsArgs a,
-                                                           ScalarGeom S, ScalarRule R, const double* __restrict__ src,
-                                                           double* __restrict__ dst, double* __restrict__ uv) {
+                                                           ScalarGeom S, ScalarRule R, ScalarSource Q,
+                                                           const double* __restrict__ src, double* __restrict__ dst,
+                                                           double* __restrict__ uv) {
     const int x = blockIdx.x, y = blockIdx.y * 256 + threadIdx.x;
     if (x >= S.ncol || y >= S.ny) return;
     const long o = (long)x * S.rows + y;
-    double g[5], pop[9], r, ux, uy;
+    double g[5], pop[9], r, ux, uy, sv = 0.0;
 #pragma unroll
     for (int i = 0; i < 5; ++i) g[i] = src[i * S.plane + o];
+    if constexpr (SOURCE) sv = Q.field[o];
     cell_state<T>(f, L, H, a, x, y, pop, r, ux, uy);
     uv[o] = ux;
     uv[S.plane + o] = uy;
-    scalar_push(g, ux, uy, S, R, x, y, dst);
+    scalar_push<SOURCE>(g, ux, uy, S, R, Q, sv, x, y, dst);
 }
 
-__global__ __launch_bounds__(256) void scalar_next_kernel(ScalarGeom S, ScalarRule R, const double* __restrict__ src,
-                                                          double* __restrict__ dst, const double* __restrict__ uv) {
+template <bool SOURCE>
+__global__ __launch_bounds__(256) void scalar_next_kernel(ScalarGeom S, ScalarRule R, ScalarSource Q,
+                                                          const double* __restrict__ src, double* __restrict__ dst,
+                                                          const double* __restrict__ uv) {
     const int x = blockIdx.x, y = blockIdx.y * 256 + threadIdx.x;
     if (x >= S.ncol || y >= S.ny) return;
     const long o = (long)x * S.rows + y;
-    double g[5];
+    double g[5], sv = 0.0;
 #pragma unroll
     for (int i = 0; i < 5; ++i) g[i] = src[i * S.plane + o];
-    scalar_push(g, uv[o], uv[S.plane + o], S, R, x, y, dst);
+    if constexpr (SOURCE) sv = Q.field[o];
+    scalar_push<SOURCE>(g, uv[o], uv[S.plane + o], S, R, Q, sv, x, y, dst);
 }
 
 // The equilibrium of C = c[x * rows + y] (device layout: plane 0 of dst's own transposed input) at the cell's
@@ -144,19 +180,30 @@ __global__ __launch_bounds__(TILE * 8) void scalar_out_kernel(const double* __re
 // The wall flux of the last substep (include/iblb.h iblb_get_scalar_wall_flux): one lane per column, which reads
 // row 0 of plane 3 and row ny - 1 of plane 4 (2 * ncol loads a column stride apart: nothing to coalesce, and a
 // thousandth of a substep's traffic).  out[x]: the wall below row 0; out[ncol + x]: the wall above the top row.
+// SOURCE: a no-flux wall returns the source's wall_flux entry, a _VALUE wall takes the source's wall_value entry.
+template <bool SOURCE>
 __global__ __launch_bounds__(256) void scalar_wall_flux_kernel(const double* __restrict__ dev, ScalarGeom S, ScalarRule R,
-                                                               double* __restrict__ out) {
+                                                               ScalarSource Q, double* __restrict__ out) {
 #pragma clang fp contract(off)
     const int x = blockIdx.x * 256 + threadIdx.x;
     if (x >= S.ncol) return;
     const double g3 = dev[3 * S.plane + (long)x * S.rows], g4 = dev[4 * S.plane + (long)x * S.rows + (S.ny - 1)];
-    out[x] = R.wall_kind[0] == IBLB_SCALAR_WALL_VALUE ? 2.0 * g3 - (2.0 * SW1) * R.wall_value[0] : 0.0;
-    out[S.ncol + x] = R.wall_kind[1] == IBLB_SCALAR_WALL_VALUE ? 2.0 * g4 - (2.0 * SW1) * R.wall_value[1] : 0.0;
+    if constexpr (SOURCE) {
+        const bool v0 = R.wall_kind[0] == IBLB_SCALAR_WALL_VALUE, v1 = R.wall_kind[1] == IBLB_SCALAR_WALL_VALUE;
+        const double e0 = Q.walls[(long)(v0 ? 2 : 0) * S.ncol + x], e1 = Q.walls[(long)(v1 ? 3 : 1) * S.ncol + x];
+        out[x] = v0 ? 2.0 * g3 - (2.0 * SW1) * e0 : e0;
+        out[S.ncol + x] = v1 ? 2.0 * g4 - (2.0 * SW1) * e1 : e1;
+    } else {
+        out[x] = R.wall_kind[0] == IBLB_SCALAR_WALL_VALUE ? 2.0 * g3 - (2.0 * SW1) * R.wall_value[0] : 0.0;
+        out[S.ncol + x] = R.wall_kind[1] == IBLB_SCALAR_WALL_VALUE ? 2.0 * g4 - (2.0 * SW1) * R.wall_value[1] : 0.0;
+    }
 }
 
 inline bool geom_ok(const ScalarGeom& S) {
     return S.ncol > 0 && S.ny > 0 && S.rows >= S.ny && S.plane >= (long)S.ncol * S.rows;
 }
+// a source has both of its arrays or neither
+inline bool source_ok(const ScalarSource& Q) { return (Q.field != nullptr) == (Q.walls != nullptr); }
 inline dim3 cell_grid(const ScalarGeom& S) { return dim3((unsigned)S.ncol, (unsigned)((S.ny + 255) / 256)); }
 inline dim3 tile_grid(int nx, int ny, int planes) {
     return dim3((unsigned)((ny + TILE - 1) / TILE), (unsigned)((nx + TILE - 1) / TILE), (unsigned)planes);
@@ -166,16 +213,18 @@ inline dim3 tile_grid(int nx, int ny, int planes) {
 
 template <typename T>
 hipError_t launch_scalar_first(const T* f, Layout L, Halo<T> H, const FieldsArgs& a, ScalarGeom S, ScalarRule R,
-                               const double* src, double* dst, double* uv, hipStream_t s) {
-    if (!geom_ok(S) || S.ncol != L.ncol || S.ny != L.ny) return hipErrorInvalidValue;
-    scalar_first_kernel<T><<<cell_grid(S), 256, 0, s>>>(f, L, H, a, S, R, src, dst, uv);
+                               ScalarSource Q, const double* src, double* dst, double* uv, hipStream_t s) {
+    if (!geom_ok(S) || S.ncol != L.ncol || S.ny != L.ny || !source_ok(Q)) return hipErrorInvalidValue;
+    if (Q.field) scalar_first_kernel<T, true><<<cell_grid(S), 256, 0, s>>>(f, L, H, a, S, R, Q, src, dst, uv);
+    else scalar_first_kernel<T, false><<<cell_grid(S), 256, 0, s>>>(f, L, H, a, S, R, Q, src, dst, uv);
     return hipGetLastError();
 }
 
-hipError_t launch_scalar_next(ScalarGeom S, ScalarRule R, const double* src, double* dst, const double* uv,
-                              hipStream_t s) {
-    if (!geom_ok(S)) return hipErrorInvalidValue;
-    scalar_next_kernel<<<cell_grid(S), 256, 0, s>>>(S, R, src, dst, uv);
+hipError_t launch_scalar_next(ScalarGeom S, ScalarRule R, ScalarSource Q, const double* src, double* dst,
+                              const double* uv, hipStream_t s) {
+    if (!geom_ok(S) || !source_ok(Q)) return hipErrorInvalidValue;
+    if (Q.field) scalar_next_kernel<true><<<cell_grid(S), 256, 0, s>>>(S, R, Q, src, dst, uv);
+    else scalar_next_kernel<false><<<cell_grid(S), 256, 0, s>>>(S, R, Q, src, dst, uv);
     return hipGetLastError();
 }
 
@@ -206,16 +255,25 @@ hipError_t launch_scalar_out(const double* dev, ScalarGeom S, int x0, int y0, in
     return hipGetLastError();
 }
 
-hipError_t launch_scalar_wall_flux(const double* dev, ScalarGeom S, ScalarRule R, double* out, hipStream_t s) {
+hipError_t launch_scalar_wall_flux(const double* dev, ScalarGeom S, ScalarRule R, ScalarSource Q, double* out,
+                                   hipStream_t s) {
+    if (!geom_ok(S) || !source_ok(Q)) return hipErrorInvalidValue;
+    const unsigned blocks = (unsigned)((S.ncol + 255) / 256);
+    if (Q.field) scalar_wall_flux_kernel<true><<<blocks, 256, 0, s>>>(dev, S, R, Q, out);
+    else scalar_wall_flux_kernel<false><<<blocks, 256, 0, s>>>(dev, S, R, Q, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_scalar_plane_out(const double* dev, ScalarGeom S, double* out, hipStream_t s) {
     if (!geom_ok(S)) return hipErrorInvalidValue;
-    scalar_wall_flux_kernel<<<(unsigned)((S.ncol + 255) / 256), 256, 0, s>>>(dev, S, R, out);
+    scalar_out_kernel<false><<<tile_grid(S.ncol, S.ny, 1), dim3(TILE, 8), 0, s>>>(dev, S, 0, 0, S.ncol, S.ny, 1, 1, out);
     return hipGetLastError();
 }
 
 template hipError_t launch_scalar_first<double>(const double*, Layout, Halo<double>, const FieldsArgs&, ScalarGeom,
-                                                ScalarRule, const double*, double*, double*, hipStream_t);
+                                                ScalarRule, ScalarSource, const double*, double*, double*, hipStream_t);
 template hipError_t launch_scalar_first<float>(const float*, Layout, Halo<float>, const FieldsArgs&, ScalarGeom,
-                                               ScalarRule, const double*, double*, double*, hipStream_t);
+                                               ScalarRule, ScalarSource, const double*, double*, double*, hipStream_t);
 template hipError_t launch_scalar_init<double>(const double*, Layout, Halo<double>, const FieldsArgs&, ScalarGeom,
                                                const double*, double*, hipStream_t);
 template hipError_t launch_scalar_init<float>(const float*, Layout, Halo<float>, const FieldsArgs&, ScalarGeom,

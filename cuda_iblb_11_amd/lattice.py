@@ -22,6 +22,11 @@ def _ptr(a: np.ndarray | None):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _addr(a: np.ndarray | None):
+    """The address of a's data for a pointer member of a ctypes struct (None: NULL); the caller keeps `a` alive."""
+    return None if a is None else a.ctypes.data
+
+
 def _window(w):
     """None, an L.Window or (x0, y0, nx, ny, sx, sy) as an L.Window (or None)."""
     if w is None or isinstance(w, L.Window):
@@ -489,7 +494,8 @@ class Lattice:
 
     def scalar_wall_flux(self) -> tuple[np.ndarray, np.ndarray]:
         """(bottom, top), [nx] each: the net amount of C that entered every column through the wall below row 0 /
-        above the top row during the last substep (iblb_get_scalar_wall_flux); exact zeros at a no-flux wall."""
+        above the top row during the last substep (iblb_get_scalar_wall_flux); exact zeros at a no-flux wall, or
+        the source's wall_flux there once `set_scalar_source` gave one."""
         bottom, top = np.empty(self.x_count), np.empty(self.x_count)
         self._check(self._lib.iblb_get_scalar_wall_flux(self._h, _ptr(bottom), _ptr(top)))
         return bottom, top
@@ -500,6 +506,44 @@ class Lattice:
         g = np.empty((5, self.ny, self.x_count))
         self._check(self._lib.iblb_get_scalar_populations(self._h, _ptr(g)))
         return g
+
+    def set_scalar_source(self, source=None, decay: float = 0.0, wall_flux=(None, None),
+                          wall_value=(None, None)) -> None:
+        """What enters and leaves the scalar from the next substep on (iblb_set_scalar_source).  source: (ny, nx),
+        the amount of C added to a cell per substep; decay: the first-order loss per substep; wall_flux: (below
+        row 0, above the top row), [nx] each or None, the amount entering a column per substep through a no-flux
+        wall; wall_value: the same pair for the walls of kind L.SCALAR_WALL_VALUE, the wall value per column.
+        Needs a scalar; replaces any previous source."""
+        def arr(a, n):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.size != n:
+                raise ValueError(f"expected {n} values, got {a.size}")
+            return a
+        source = arr(source, self.N)
+        f0, f1 = (arr(a, self.x_count) for a in wall_flux)
+        v0, v1 = (arr(a, self.x_count) for a in wall_value)
+        src = L.ScalarSource(_addr(source), float(decay), (C.c_void_p * 2)(_addr(f0), _addr(f1)),
+                             (C.c_void_p * 2)(_addr(v0), _addr(v1)))
+        self._check(self._lib.iblb_set_scalar_source(self._h, C.byref(src)))
+
+    def remove_scalar_source(self) -> None:
+        """Remove the source: the scalar's substep is then exactly what it is without one."""
+        self._check(self._lib.iblb_set_scalar_source(self._h, None))
+
+    def scalar_source_info(self) -> dict:
+        """{"decay", "present"} of the source (iblb_scalar_source_info); present: L.SCALAR_SOURCE_* bits, 0: none
+        set."""
+        k, m = C.c_double(0.0), C.c_uint(0)
+        self._check(self._lib.iblb_scalar_source_info(self._h, C.byref(k), C.byref(m)))
+        return {"decay": k.value, "present": m.value}
+
+    def scalar_source(self) -> np.ndarray:
+        """The bulk source as given, (ny, nx) (iblb_get_scalar_source); zeros where the source has none."""
+        out = np.empty((self.ny, self.x_count))
+        self._check(self._lib.iblb_get_scalar_source(self._h, _ptr(out)))
+        return out
 
     @property
     def steps(self) -> int:

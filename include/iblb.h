@@ -494,6 +494,50 @@ int iblb_get_scalar_populations(iblb_ctx* ctx, double* g);
 int iblb_scalar_info(iblb_ctx* ctx, iblb_scalar* cfg, long long* updates);
 int iblb_get_scalar_wall_flux(iblb_ctx* ctx, double* bottom, double* top);
 
+/* The scalar's source: what enters and leaves C other than through a wall held at one uniform value.  A bulk source
+ * per cell, a first-order decay, a prescribed flux per column through a no-flux wall, and a wall value per column at
+ * a _VALUE wall; each costs no readback and keeps the deep sweep. */
+typedef struct iblb_scalar_source {
+    const double* source;         /* [N], j = y*XDIM + x: amount of C added to the cell per substep; NULL = 0 */
+    double        decay;          /* k: finite, >= 0; first-order loss per substep                            */
+    const double* wall_flux[2];   /* [XDIM] each, only where the scalar's wall kind is _NOFLUX: amount of C
+                                     entering column x through that wall per substep (negative: leaving);
+                                     NULL = 0, the no-flux wall                                               */
+    const double* wall_value[2];  /* [XDIM] each, only where the wall kind is _VALUE: the wall value of
+                                     column x in place of iblb_scalar.wall_value[k]; NULL = the uniform one   */
+} iblb_scalar_source;             /* [0]: wall below row 0, [1]: wall above row YDIM-1 */
+/* iblb_set_scalar_source needs a scalar (IBLB_ERR_STATE otherwise; that covers the slabs of a group, which cannot
+ * hold one).  It copies its arrays to the device, replaces any previous source and takes effect from the next
+ * substep that runs; it moves neither t0 nor the event count.  src == NULL removes the source.  decay not finite or
+ * negative, a non-finite entry in any array, wall_flux[k] given for a _VALUE wall, wall_value[k] given for a _NOFLUX
+ * wall: IBLB_ERR_ARG, checked before anything is touched.  The new device buffers are allocated before the old ones
+ * are freed: any error, IBLB_ERR_NOMEM included, leaves the previous source as it was.
+ * Update rule.  With a source set, one substep replaces the relaxation line and the two wall lines of the rule of
+ * iblb_set_scalar by (every operation in double, rounded once, no contraction):
+ *   m   = decay*C
+ *   r   = s(x,y) - m                                          s = 0.0 where `source` is NULL
+ *   p_i = (g_i - omega*(g_i - geq_i)) + w_i*r
+ *   g_3'(x, 0)      = p_4(x, 0) + wall_flux[0][x]             _NOFLUX (0.0 where NULL)
+ *                   = (2.0*w1)*wall_value[0][x] - p_4(x, 0)   _VALUE  (the uniform value where NULL)
+ *   g_4'(x, YDIM-1) = likewise with p_3 and index [1]
+ * The rule is applied in full whenever a source is set: no term is skipped for a NULL array or for decay == 0, so
+ * results are pinned by value (==); the sign of a zero is not part of the contract.  With no source set the substep
+ * is exactly the rule of iblb_set_scalar.  Between walls of kind _NOFLUX sum(C) changes per substep by
+ * sum(r) + sum_x(wall_flux[0][x] + wall_flux[1][x]), up to rounding.  A substep with a source reads one more plane:
+ * 104 bytes per cell.
+ * iblb_get_scalar_wall_flux with a source set: a _NOFLUX wall returns wall_flux[k][x] exactly (0.0 where NULL), a
+ * _VALUE wall uses wall_value[k][x] in its expression.
+ * iblb_set_scalar removes the source with the scalar it belonged to, whether it replaces or removes the scalar (a
+ * replacement may change the wall kinds: set the source again).  iblb_set_state keeps the source,
+ * iblb_load_checkpoint removes it along with the scalar, iblb_destroy frees it.
+ * iblb_scalar_source_info (either pointer may be NULL): decay, and present = 1 (a source is set) | 2 (`source`)
+ * | 4, 8 (wall_flux[0], [1]) | 16, 32 (wall_value[0], [1]); no source set: 0 and 0.0.
+ * iblb_get_scalar_source returns `source` [N] in the reference layout, zeros where the source was set without it.
+ * No source set: IBLB_ERR_STATE; source == NULL: IBLB_ERR_ARG. */
+int iblb_set_scalar_source(iblb_ctx* ctx, const iblb_scalar_source* src);
+int iblb_scalar_source_info(iblb_ctx* ctx, double* decay, unsigned* present);
+int iblb_get_scalar_source(iblb_ctx* ctx, double* source);
+
 /* Timing: when enabled (1) every collide-stream launch is bracketed by HIP events on the
  * stream it runs on; iblb_get_timing() returns the sums (and resets them if reset).  enabled = 2:
  * only the deep (K-iteration) launches are timed, by their own dispatch / completion signals (no
