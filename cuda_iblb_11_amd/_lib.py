@@ -116,6 +116,16 @@ SCALAR_SOURCE_WALL_FLUX = (4, 8)
 SCALAR_SOURCE_WALL_VALUE = (16, 32)
 
 
+class ScalarUptake(C.Structure):
+    """struct iblb_scalar_uptake (include/iblb.h)."""
+    _fields_ = [("rate", C.c_void_p * 2)]
+
+
+# the `present` bits of iblb_scalar_uptake_info
+SCALAR_UPTAKE_SET = 1
+SCALAR_UPTAKE_RATE = (2, 4)
+
+
 class FieldStats(C.Structure):
     """struct iblb_field_stats (include/iblb.h)."""
     _fields_ = [
@@ -181,6 +191,10 @@ _SIGS = {
     "iblb_set_scalar_source": ([_vp, C.POINTER(ScalarSource)], C.c_int),
     "iblb_scalar_source_info": ([_vp, C.POINTER(C.c_double), C.POINTER(C.c_uint)], C.c_int),
     "iblb_get_scalar_source": ([_vp, _vp], C.c_int),
+    "iblb_set_scalar_uptake": ([_vp, C.POINTER(ScalarUptake)], C.c_int),
+    "iblb_get_scalar_uptake": ([_vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_longlong)], C.c_int),
+    "iblb_reset_scalar_uptake": ([_vp], C.c_int),
+    "iblb_scalar_uptake_info": ([_vp, C.POINTER(C.c_uint), C.POINTER(C.c_longlong)], C.c_int),
     "iblb_set_profiling": ([_vp, C.c_int], C.c_int),
     "iblb_get_timing": ([_vp, C.POINTER(Timing), C.c_int], C.c_int),
     "iblb_get_timing_ex": ([_vp, C.POINTER(Timing), C.c_ulong, C.c_int], C.c_int),

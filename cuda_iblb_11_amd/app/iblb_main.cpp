@@ -46,6 +46,11 @@
 // `flux` of C enters every column through the bottom wall per substep, and C decays everywhere at the first-order
 // rate `decay` per substep (default 0); both finite, decay >= 0.  Everything else about IBLB_SCALAR stays as it is;
 // with both set, sum(C) in <..>-cstats.dat tends to flux XDIM / decay.
+// IBLB_SCALAR_UPTAKE=k_bottom[,k_top] (needs IBLB_SCALAR) makes the walls absorb that scalar (iblb_set_scalar_uptake):
+// every column loses k * C at the wall per substep through the bottom / the top wall (default 0); both finite and
+// >= 0.  At every output iteration <it>-uptake.dat beside <it>-scalar.dat holds one line per column (%.17g),
+//   x  total_bottom  total_top
+// the net amount of C that entered the column through each wall since the run's first iteration (negative: absorbed).
 #include <sys/stat.h>
 #include <sys/time.h>
 #include <unistd.h>
@@ -323,6 +328,36 @@ int main(int argc, char* argv[]) {
         sc_source = true;
     }
 
+    // the scalar's uptake (extension): uniform first-order rates at the two no-flux walls
+    bool sc_uptake = false;
+    double sc_rate[2] = {0., 0.};
+    if (const char* ss = getenv("IBLB_SCALAR_UPTAKE"); ss && *ss) {
+        // one or two finite numbers >= 0 separated by a comma, nothing else
+        const char* p = ss;
+        bool ok = true;
+        for (int n = 0; ok; ++n) {
+            char* end = nullptr;
+            errno = 0;
+            const double v = strtod(p, &end);
+            ok = n < 2 && ((*p >= '0' && *p <= '9') || *p == '.' || *p == '+') && end != p && errno == 0 &&
+                 std::isfinite(v) && v >= 0. && (*end == ',' || *end == 0);
+            if (!ok) break;
+            sc_rate[n] = v;
+            if (*end == 0) break;
+            p = end + 1;
+        }
+        if (!ok) {
+            if (lead)
+                cerr << "IBLB_SCALAR_UPTAKE must be k_bottom[,k_top], both finite and >= 0, got " << ss << endl;
+            return 2;
+        }
+        if (!(sc_tau > 0.)) {
+            if (lead) cerr << "IBLB_SCALAR_UPTAKE needs IBLB_SCALAR: there is no scalar to absorb" << endl;
+            return 2;
+        }
+        sc_uptake = true;
+    }
+
     const double dx = 1. / LENGTH;
     const double dt = 1. / (T);
     const double SPEED = 0.8 * 1000 / T;
@@ -419,6 +454,8 @@ int main(int argc, char* argv[]) {
     // iteration (a restarted run's too: checkpoints hold no scalar)
     iblb_window sc_win{0, 0, ((int)XDIM - 1) / sc_sx + 1, ((int)YDIM - 1) / sc_sy + 1, sc_sx, sc_sy};
     std::vector<double> sc_out(sc_tau > 0. ? (size_t)sc_win.nx * sc_win.ny : 0);
+    std::vector<double> up_total[2];
+    for (auto& v : up_total) v.assign(sc_uptake ? (size_t)XDIM : 0, 0.);
     if (sc_tau > 0.) {
         std::vector<double> c0((size_t)size);
         for (int j = 0; j < size; j++) c0[j] = (unsigned int)j / XDIM < YDIM / 2 ? 1. : 0.;
@@ -428,6 +465,11 @@ int main(int argc, char* argv[]) {
             const std::vector<double> influx((size_t)XDIM, sc_flux);
             const iblb_scalar_source src{nullptr, sc_decay, {influx.data(), nullptr}, {nullptr, nullptr}};
             if ((rc = iblb_set_scalar_source(ctx, &src))) return die(ctx, rc, "iblb_set_scalar_source");
+        }
+        if (sc_uptake) {
+            const std::vector<double> k0((size_t)XDIM, sc_rate[0]), k1((size_t)XDIM, sc_rate[1]);
+            const iblb_scalar_uptake up{{k0.data(), k1.data()}};
+            if ((rc = iblb_set_scalar_uptake(ctx, &up))) return die(ctx, rc, "iblb_set_scalar_uptake");
         }
     }
 
@@ -634,6 +676,19 @@ int main(int argc, char* argv[]) {
                     for (int i = 0; i < sc_win.nx; i++)
                         fprintf(fc, "%d\t%d\t%.17g\n", i * sc_sx, j * sc_sy, sc_out[(size_t)j * sc_win.nx + i]);
                 fclose(fc);
+            }
+            if (sc_uptake) {
+                if ((rc = iblb_get_scalar_uptake(ctx, up_total[0].data(), up_total[1].data(), nullptr, nullptr, nullptr)))
+                    return die(ctx, rc, "iblb_get_scalar_uptake");
+                outfile = raw_data + to_string(it) + "-uptake.dat";
+                FILE* fu = fopen(outfile.c_str(), "w");
+                if (!fu) {
+                    fprintf(stderr, "cannot write %s: %s\n", outfile.c_str(), strerror(errno));
+                    return 1;
+                }
+                for (size_t i = 0; i < (size_t)XDIM; i++)
+                    fprintf(fu, "%zu\t%.17g\t%.17g\n", i, up_total[0][i], up_total[1][i]);
+                fclose(fu);
             }
             if (av_stride > 0 && !av_first) {
                 outfile = raw_data + to_string(it) + "-mean.dat";

@@ -226,6 +226,12 @@ struct iblb_ctx {
     double* sc_src_walls = nullptr;
     double sc_src_decay = 0.0;
     unsigned sc_src_present = 0;  // the `present` bits of iblb_scalar_source_info
+    // the scalar's uptake (iblb_set_scalar_uptake).  sc_up_present == 0: none.  sc_up: one allocation of [6 * ncol],
+    // a, total, last of ScalarUptake ([2 * ncol] each, wall 0 then wall 1); a NULL rate array of the call is held as
+    // zeros in a.  Lives and dies with the scalar.
+    double* sc_up = nullptr;
+    unsigned sc_up_present = 0;   // the `present` bits of iblb_scalar_uptake_info
+    long long sc_up_substeps = 0; // substeps accumulated since the set / the reset
     // state machine
     int phase = iblbh::PH_EMPTY;
     long long t = 0;

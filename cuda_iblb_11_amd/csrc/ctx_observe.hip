@@ -19,8 +19,16 @@ static void scalar_source_free(iblb_ctx* c) {
     c->sc_src_present = 0;
 }
 
+static void scalar_uptake_free(iblb_ctx* c) {
+    if (c->sc_up) (void)hipFree(c->sc_up);
+    c->sc_up = nullptr;
+    c->sc_up_present = 0;
+    c->sc_up_substeps = 0;
+}
+
 void scalar_free(iblb_ctx* c) {
     scalar_source_free(c);  // the source belongs to the scalar it was set on
+    scalar_uptake_free(c);  // and so does the uptake
     if (c->sc_alloc) (void)hipFree(c->sc_alloc);
     c->sc_alloc = c->sc_g[0] = c->sc_g[1] = c->sc_uv = nullptr;
     c->sc_cur = 0;
@@ -39,6 +47,13 @@ static ScalarRule scalar_rule(const iblb_scalar& k) {
 // nullptr members without a source: the launchers then run the builds without one
 static ScalarSource scalar_source(const iblb_ctx* c) {
     return ScalarSource{c->sc_src_field, c->sc_src_walls, c->sc_src_decay};
+}
+
+// nullptr members without an uptake: the launchers then run the builds without one
+static ScalarUptake scalar_uptake(const iblb_ctx* c) {
+    if (!c->sc_up) return ScalarUptake{nullptr, nullptr, nullptr};
+    const size_t n = 2 * (size_t)c->ncol;
+    return ScalarUptake{c->sc_up, c->sc_up + n, c->sc_up + 2 * n};
 }
 
 void tracers_free(iblb_ctx* c) {
@@ -101,7 +116,8 @@ static int average_update(iblb_ctx* c) {
 // One event of the scalar on the context's stream: the state prepared as for a reader (the band streams
 // joined, the owed IB force evaluated), then `stride` substeps with the velocity of this state: the first
 // evaluates it from the fluid populations and leaves it in the scratch, the others read the scratch.  With a source
-// (iblb_set_scalar_source) every substep runs the SOURCE build, without one the build that has none.
+// (iblb_set_scalar_source) every substep runs the SOURCE build, without one the build that has none; likewise the
+// UPTAKE builds with an uptake (iblb_set_scalar_uptake), whose accumulators then take every substep of the event.
 static int scalar_update(iblb_ctx* c) {
     if (!single_slab(c))  // the context joined a group after iblb_set_scalar: its lattice is the whole lattice's
         return fail(c, IBLB_ERR_UNSUPPORTED, "scalar: a lone slab only; remove it before joining a group");
@@ -111,15 +127,18 @@ static int scalar_update(iblb_ctx* c) {
     const ScalarGeom S = scalar_geom(c);
     const ScalarRule R = scalar_rule(c->sc_cfg);
     const ScalarSource Q = scalar_source(c);
+    const ScalarUptake U = scalar_uptake(c);
     HIP_TRY(c, with_state(c, [&](auto* g, auto H) {
-        return launch_scalar_first(g, c->L, H, a, S, R, Q, c->sc_g[c->sc_cur], c->sc_g[c->sc_cur ^ 1], c->sc_uv, c->stream);
+        return launch_scalar_first(g, c->L, H, a, S, R, Q, U, c->sc_g[c->sc_cur], c->sc_g[c->sc_cur ^ 1], c->sc_uv,
+                                   c->stream);
     }));
     c->sc_cur ^= 1;
     for (int k = 1; k < c->sc_ev.stride; ++k) {
-        HIP_TRY(c, launch_scalar_next(S, R, Q, c->sc_g[c->sc_cur], c->sc_g[c->sc_cur ^ 1], c->sc_uv, c->stream));
+        HIP_TRY(c, launch_scalar_next(S, R, Q, U, c->sc_g[c->sc_cur], c->sc_g[c->sc_cur ^ 1], c->sc_uv, c->stream));
         c->sc_cur ^= 1;
     }
     c->sc_ev.advance();
+    if (c->sc_up) c->sc_up_substeps += c->sc_ev.stride;
     return IBLB_OK;
 }
 
@@ -409,6 +428,15 @@ int iblb_scalar_info(iblb_ctx* c, iblb_scalar* cfg, long long* updates) {
     return IBLB_OK;
 }
 
+// a_k[x] of iblb_set_scalar_uptake from the rate k: 2.0 - 2.0/(1.0 + 3.0*k), every operation in double and rounded
+// once.  The volatiles keep the host compiler from contracting 1.0 + 3.0*k into one fused operation.
+static double uptake_coefficient(double k) {
+    volatile double t = 3.0 * k;
+    volatile double d = 1.0 + t;
+    volatile double q = 2.0 / d;
+    return 2.0 - q;
+}
+
 // ---- the scalar's source ------------------------------------------------------------------------------
 static bool all_finite(const double* a, size_t n) {
     for (size_t j = 0; j < n; ++j)
@@ -497,6 +525,85 @@ int iblb_get_scalar_source(iblb_ctx* c, double* source) {
     HIP_TRY(c, hipMalloc(&d.p, nb));
     HIP_TRY(c, launch_scalar_plane_out(c->sc_src_field, scalar_geom(c), (double*)d.p, c->stream));
     return read_back(c, source, d.p, nb);
+}
+
+// ---- the scalar's uptake ------------------------------------------------------------------------------
+int iblb_set_scalar_uptake(iblb_ctx* c, const iblb_scalar_uptake* up) {
+    if (!c) return IBLB_ERR_ARG;
+    if (!c->sc_alloc)
+        return fail(c, IBLB_ERR_STATE, single_slab(c) ? "iblb_set_scalar_uptake: no scalar is set (iblb_set_scalar)"
+                                                      : "iblb_set_scalar_uptake: a slab of a group holds no scalar");
+    const size_t ncol = (size_t)c->ncol;
+    if (up) {
+        for (int k = 0; k < 2; ++k) {
+            if (!up->rate[k]) continue;
+            if (c->sc_cfg.wall_kind[k] == IBLB_SCALAR_WALL_VALUE)
+                return fail(c, IBLB_ERR_ARG, "rate is given for a wall of kind IBLB_SCALAR_WALL_VALUE");
+            for (size_t x = 0; x < ncol; ++x)
+                if (!std::isfinite(up->rate[k][x]) || up->rate[k][x] < 0.0)
+                    return fail(c, IBLB_ERR_ARG, "rate holds an entry that is not finite or is negative");
+        }
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (!up) {
+        scalar_uptake_free(c);
+        return IBLB_OK;
+    }
+    // a, total, last side by side; a of a NULL rate array and both accumulators start as zeros
+    std::vector<double> host(6 * ncol, 0.0);
+    unsigned present = 1u;
+    for (int k = 0; k < 2; ++k) {
+        if (!up->rate[k]) continue;
+        for (size_t x = 0; x < ncol; ++x) host[(size_t)k * ncol + x] = uptake_coefficient(up->rate[k][x]);
+        present |= 2u << k;
+    }
+    // the new buffer first: a failed allocation leaves the previous uptake as it was
+    DevBuf d;
+    HIP_TRY(c, hipMalloc(&d.p, 6 * ncol * sizeof(double)));
+    HIP_TRY(c, hipMemcpyAsync(d.p, host.data(), 6 * ncol * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    scalar_uptake_free(c);
+    c->sc_up = (double*)d.p;
+    d.p = nullptr;
+    c->sc_up_present = present;
+    return IBLB_OK;
+}
+
+int iblb_reset_scalar_uptake(iblb_ctx* c) {
+    if (!c) return IBLB_ERR_ARG;
+    if (!c->sc_up) return fail(c, IBLB_ERR_STATE, "iblb_reset_scalar_uptake: no uptake is set");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n = 2 * (size_t)c->ncol;  // total and last follow a
+    HIP_TRY(c, hipMemsetAsync(c->sc_up + n, 0, 2 * n * sizeof(double), c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->sc_up_substeps = 0;
+    return IBLB_OK;
+}
+
+int iblb_get_scalar_uptake(iblb_ctx* c, double* total_bottom, double* total_top, double* last_bottom, double* last_top,
+                           long long* substeps) {
+    if (!c) return IBLB_ERR_ARG;
+    if (!c->sc_up) return fail(c, IBLB_ERR_STATE, "iblb_get_scalar_uptake: no uptake is set");
+    if (!total_bottom && !total_top && !last_bottom && !last_top && !substeps)
+        return fail(c, IBLB_ERR_ARG, "every output is NULL");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const ScalarUptake U = scalar_uptake(c);
+    const size_t nb = (size_t)c->ncol * sizeof(double);
+    int rc = read_back(c, {{total_bottom, U.total, nb},
+                           {total_top, U.total + c->ncol, nb},
+                           {last_bottom, U.last, nb},
+                           {last_top, U.last + c->ncol, nb}});
+    if (rc) return rc;
+    if (substeps) *substeps = c->sc_up_substeps;
+    return IBLB_OK;
+}
+
+int iblb_scalar_uptake_info(iblb_ctx* c, unsigned* present, long long* substeps) {
+    if (!c) return IBLB_ERR_ARG;
+    if (present) *present = c->sc_up_present;
+    if (substeps) *substeps = c->sc_up_substeps;
+    return IBLB_OK;
 }
 
 }  // extern "C"

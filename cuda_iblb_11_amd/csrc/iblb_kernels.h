@@ -282,13 +282,23 @@ struct ScalarSource {
     const double* walls;  // [4 * ncol]: wall_flux[0], wall_flux[1], wall_value[0], wall_value[1], [ncol] each
     double decay;
 };
+// The scalar's uptake (include/iblb.h iblb_set_scalar_uptake).  a == nullptr: none, and every launch below runs the
+// build without it.  Otherwise all three members are set, [2 * ncol] each, index k * ncol + x for wall k (0: below
+// row 0, 1: above row ny - 1): a NULL rate array of the ABI is held as zeros in `a`.
+struct ScalarUptake {
+    const double* a;  // a_k[x] = 2.0 - 2.0/(1.0 + 3.0*rate[k][x]), computed on the host
+    double* total;    // what crossed wall k of column x since the set / the reset
+    double* last;     // ... during the last substep
+};
 // One substep src -> dst (distinct buffers).  first: the velocity from the fluid state by cell_state of
 // field_eval.h (of FieldsArgs the window members are unused), also left in uv; next: the velocity read from uv.
+// With an uptake the lanes of rows 0 and ny - 1 also update U.total and U.last, one writer per entry.
 template <typename T>
 hipError_t launch_scalar_first(const T* f, Layout L, Halo<T> H, const FieldsArgs& a, ScalarGeom S, ScalarRule R,
-                               ScalarSource Q, const double* src, double* dst, double* uv, hipStream_t s);
-hipError_t launch_scalar_next(ScalarGeom S, ScalarRule R, ScalarSource Q, const double* src, double* dst,
-                              const double* uv, hipStream_t s);
+                               ScalarSource Q, ScalarUptake U, const double* src, double* dst, double* uv,
+                               hipStream_t s);
+hipError_t launch_scalar_next(ScalarGeom S, ScalarRule R, ScalarSource Q, ScalarUptake U, const double* src,
+                              double* dst, const double* uv, hipStream_t s);
 // dst's five planes = the equilibrium of C = c[x * rows + y] at the fluid state's velocity; c may be dst's plane 0.
 template <typename T>
 hipError_t launch_scalar_init(const T* f, Layout L, Halo<T> H, const FieldsArgs& a, ScalarGeom S, const double* c,

@@ -20,6 +20,12 @@
 // 4 * ncol array (the flux or the value, by the wall's kind).  Every term of the rule is evaluated: what the call
 // left NULL is an array of zeros (or of the uniform wall value) on the device.  Without a source the builds
 // without SOURCE run: the kernels as they were.
+// With an uptake (iblb_set_scalar_uptake) the UPTAKE builds run: the lanes of rows 0 and ny - 1 also load their
+// column's coefficient a and running total from the uptake's arrays ([2 * ncol] each) and store the total and the
+// substep's net amount: four more 8-byte accesses per wall lane, a column stride apart like those of
+// scalar_wall_flux_kernel, 2 / ny of a substep's traffic.  Every entry has one writer per substep (with ny == 1 one
+// lane writes both walls' entries) and successive substeps are ordered by the stream: no atomics, and the sums are
+// bit-reproducible.  Without an uptake the builds without UPTAKE run: the kernels as they were.
 //
 // The transposes between the ABI's layouts ([y * nx + x]) and the device's go through an LDS tile so that both
 // sides coalesce.
@@ -32,13 +38,34 @@ namespace {
 constexpr int TILE = 32;  // transposes: TILE x TILE elements per workgroup of TILE x 8 lanes
 constexpr double SW0 = 1.0 / 3.0, SW1 = 1.0 / 6.0;
 
+// One wall lane's store under an uptake (include/iblb.h iblb_set_scalar_uptake).  q: the population that would leave
+// through the wall; e: the column's entry of the rule in force (the flux at a no-flux wall, the value at a _VALUE
+// wall; without a source 0.0 and the uniform value); w: the column's index into the uptake's arrays.  Returns what
+// the opposite direction of the same cell receives, and adds the net amount that entered to the column's total.
+__device__ __forceinline__ double uptake_wall(double q, double e, bool value, const ScalarUptake& U, long w) {
+#pragma clang fp contract(off)
+    double out, net;
+    if (value) {
+        out = (2.0 * SW1) * e - q;
+        net = out - q;
+    } else {
+        const double l = U.a[w] * q;
+        out = (q - l) + e;
+        net = e - l;
+    }
+    U.total[w] = U.total[w] + net;
+    U.last[w] = net;
+    return out;
+}
+
 // One cell of a substep: g[5] of cell (x, y) relaxed towards the equilibrium at (ux, uy) and pushed into dst.
 // SOURCE: the rule of iblb_set_scalar_source.  sv = s(x, y) of the lane's cell; the lanes of rows 0 and ny - 1 load
 // their column's one wall entry (the flux or the value, by the wall's kind) from Q.walls.
-template <bool SOURCE>
+// UPTAKE: the rule of iblb_set_scalar_uptake at those two rows, with or without a source.
+template <bool SOURCE, bool UPTAKE>
 __device__ __forceinline__ void scalar_push(const double g[5], double ux, double uy, const ScalarGeom& S,
-                                            const ScalarRule& R, const ScalarSource& Q, double sv, int x, int y,
-                                            double* __restrict__ dst) {
+                                            const ScalarRule& R, const ScalarSource& Q, const ScalarUptake& U,
+                                            double sv, int x, int y, double* __restrict__ dst) {
 #pragma clang fp contract(off)
     const double C = (((g[0] + g[1]) + g[2]) + g[3]) + g[4];
     const double a[5] = {0.0, ux, -ux, uy, -uy};
@@ -60,7 +87,22 @@ __device__ __forceinline__ void scalar_push(const double g[5], double ux, double
     dst[o] = p[0];
     dst[S.plane + oxp] = p[1];
     dst[2 * S.plane + oxm] = p[2];
-    if constexpr (SOURCE) {
+    if constexpr (UPTAKE) {
+        if (y + 1 < S.ny) dst[3 * S.plane + o + 1] = p[3];
+        else {
+            const bool value = R.wall_kind[1] == IBLB_SCALAR_WALL_VALUE;
+            double e = value ? R.wall_value[1] : 0.0;
+            if constexpr (SOURCE) e = Q.walls[(long)(value ? 3 : 1) * S.ncol + x];
+            dst[4 * S.plane + o] = uptake_wall(p[3], e, value, U, (long)S.ncol + x);
+        }
+        if (y > 0) dst[4 * S.plane + o - 1] = p[4];
+        else {
+            const bool value = R.wall_kind[0] == IBLB_SCALAR_WALL_VALUE;
+            double e = value ? R.wall_value[0] : 0.0;
+            if constexpr (SOURCE) e = Q.walls[(long)(value ? 2 : 0) * S.ncol + x];
+            dst[3 * S.plane + o] = uptake_wall(p[4], e, value, U, (long)x);
+        }
+    } else if constexpr (SOURCE) {
         if (y + 1 < S.ny) dst[3 * S.plane + o + 1] = p[3];
         else {
             const bool value = R.wall_kind[1] == IBLB_SCALAR_WALL_VALUE;
@@ -82,12 +124,12 @@ __device__ __forceinline__ void scalar_push(const double g[5], double ux, double
 }
 
 // grid: (ncol, ceil(ny / 256)); one lane per cell.  The SOURCE builds load one more plane, Q.field; the others
-// never touch Q.
-template <typename T, bool SOURCE>
+// never touch Q.  U stands last: the builds without UPTAKE never touch it, and their other arguments keep their places.
+template <typename T, bool SOURCE, bool UPTAKE>
 __global__ __launch_bounds__(256) void scalar_first_kernel(const T* __restrict__ f, Layout L, Halo<T> H, FieldsArgs a,
                                                            ScalarGeom S, ScalarRule R, ScalarSource Q,
                                                            const double* __restrict__ src, double* __restrict__ dst,
-                                                           double* __restrict__ uv) {
+                                                           double* __restrict__ uv, ScalarUptake U) {
     const int x = blockIdx.x, y = blockIdx.y * 256 + threadIdx.x;
     if (x >= S.ncol || y >= S.ny) return;
     const long o = (long)x * S.rows + y;
@@ -98,13 +140,13 @@ __global__ __launch_bounds__(256) void scalar_first_kernel(const T* __restrict__
     cell_state<T>(f, L, H, a, x, y, pop, r, ux, uy);
     uv[o] = ux;
     uv[S.plane + o] = uy;
-    scalar_push<SOURCE>(g, ux, uy, S, R, Q, sv, x, y, dst);
+    scalar_push<SOURCE, UPTAKE>(g, ux, uy, S, R, Q, U, sv, x, y, dst);
 }
 
-template <bool SOURCE>
+template <bool SOURCE, bool UPTAKE>
 __global__ __launch_bounds__(256) void scalar_next_kernel(ScalarGeom S, ScalarRule R, ScalarSource Q,
                                                           const double* __restrict__ src, double* __restrict__ dst,
-                                                          const double* __restrict__ uv) {
+                                                          const double* __restrict__ uv, ScalarUptake U) {
     const int x = blockIdx.x, y = blockIdx.y * 256 + threadIdx.x;
     if (x >= S.ncol || y >= S.ny) return;
     const long o = (long)x * S.rows + y;
@@ -112,7 +154,7 @@ __global__ __launch_bounds__(256) void scalar_next_kernel(ScalarGeom S, ScalarRu
 #pragma unroll
     for (int i = 0; i < 5; ++i) g[i] = src[i * S.plane + o];
     if constexpr (SOURCE) sv = Q.field[o];
-    scalar_push<SOURCE>(g, uv[o], uv[S.plane + o], S, R, Q, sv, x, y, dst);
+    scalar_push<SOURCE, UPTAKE>(g, uv[o], uv[S.plane + o], S, R, Q, U, sv, x, y, dst);
 }
 
 // The equilibrium of C = c[x * rows + y] (device layout: plane 0 of dst's own transposed input) at the cell's
@@ -204,6 +246,10 @@ inline bool geom_ok(const ScalarGeom& S) {
 }
 // a source has both of its arrays or neither
 inline bool source_ok(const ScalarSource& Q) { return (Q.field != nullptr) == (Q.walls != nullptr); }
+// an uptake has all three of its arrays or none
+inline bool uptake_ok(const ScalarUptake& U) {
+    return (U.a != nullptr) == (U.total != nullptr) && (U.a != nullptr) == (U.last != nullptr);
+}
 inline dim3 cell_grid(const ScalarGeom& S) { return dim3((unsigned)S.ncol, (unsigned)((S.ny + 255) / 256)); }
 inline dim3 tile_grid(int nx, int ny, int planes) {
     return dim3((unsigned)((ny + TILE - 1) / TILE), (unsigned)((nx + TILE - 1) / TILE), (unsigned)planes);
@@ -213,18 +259,31 @@ inline dim3 tile_grid(int nx, int ny, int planes) {
 
 template <typename T>
 hipError_t launch_scalar_first(const T* f, Layout L, Halo<T> H, const FieldsArgs& a, ScalarGeom S, ScalarRule R,
-                               ScalarSource Q, const double* src, double* dst, double* uv, hipStream_t s) {
-    if (!geom_ok(S) || S.ncol != L.ncol || S.ny != L.ny || !source_ok(Q)) return hipErrorInvalidValue;
-    if (Q.field) scalar_first_kernel<T, true><<<cell_grid(S), 256, 0, s>>>(f, L, H, a, S, R, Q, src, dst, uv);
-    else scalar_first_kernel<T, false><<<cell_grid(S), 256, 0, s>>>(f, L, H, a, S, R, Q, src, dst, uv);
+                               ScalarSource Q, ScalarUptake U, const double* src, double* dst, double* uv,
+                               hipStream_t s) {
+    if (!geom_ok(S) || S.ncol != L.ncol || S.ny != L.ny || !source_ok(Q) || !uptake_ok(U)) return hipErrorInvalidValue;
+    const dim3 grid = cell_grid(S);
+    if (U.a) {
+        if (Q.field) scalar_first_kernel<T, true, true><<<grid, 256, 0, s>>>(f, L, H, a, S, R, Q, src, dst, uv, U);
+        else scalar_first_kernel<T, false, true><<<grid, 256, 0, s>>>(f, L, H, a, S, R, Q, src, dst, uv, U);
+    } else {
+        if (Q.field) scalar_first_kernel<T, true, false><<<grid, 256, 0, s>>>(f, L, H, a, S, R, Q, src, dst, uv, U);
+        else scalar_first_kernel<T, false, false><<<grid, 256, 0, s>>>(f, L, H, a, S, R, Q, src, dst, uv, U);
+    }
     return hipGetLastError();
 }
 
-hipError_t launch_scalar_next(ScalarGeom S, ScalarRule R, ScalarSource Q, const double* src, double* dst,
-                              const double* uv, hipStream_t s) {
-    if (!geom_ok(S) || !source_ok(Q)) return hipErrorInvalidValue;
-    if (Q.field) scalar_next_kernel<true><<<cell_grid(S), 256, 0, s>>>(S, R, Q, src, dst, uv);
-    else scalar_next_kernel<false><<<cell_grid(S), 256, 0, s>>>(S, R, Q, src, dst, uv);
+hipError_t launch_scalar_next(ScalarGeom S, ScalarRule R, ScalarSource Q, ScalarUptake U, const double* src,
+                              double* dst, const double* uv, hipStream_t s) {
+    if (!geom_ok(S) || !source_ok(Q) || !uptake_ok(U)) return hipErrorInvalidValue;
+    const dim3 grid = cell_grid(S);
+    if (U.a) {
+        if (Q.field) scalar_next_kernel<true, true><<<grid, 256, 0, s>>>(S, R, Q, src, dst, uv, U);
+        else scalar_next_kernel<false, true><<<grid, 256, 0, s>>>(S, R, Q, src, dst, uv, U);
+    } else {
+        if (Q.field) scalar_next_kernel<true, false><<<grid, 256, 0, s>>>(S, R, Q, src, dst, uv, U);
+        else scalar_next_kernel<false, false><<<grid, 256, 0, s>>>(S, R, Q, src, dst, uv, U);
+    }
     return hipGetLastError();
 }
 
@@ -271,9 +330,11 @@ hipError_t launch_scalar_plane_out(const double* dev, ScalarGeom S, double* out,
 }
 
 template hipError_t launch_scalar_first<double>(const double*, Layout, Halo<double>, const FieldsArgs&, ScalarGeom,
-                                                ScalarRule, ScalarSource, const double*, double*, double*, hipStream_t);
+                                                ScalarRule, ScalarSource, ScalarUptake, const double*, double*, double*,
+                                                hipStream_t);
 template hipError_t launch_scalar_first<float>(const float*, Layout, Halo<float>, const FieldsArgs&, ScalarGeom,
-                                               ScalarRule, ScalarSource, const double*, double*, double*, hipStream_t);
+                                               ScalarRule, ScalarSource, ScalarUptake, const double*, double*, double*,
+                                               hipStream_t);
 template hipError_t launch_scalar_init<double>(const double*, Layout, Halo<double>, const FieldsArgs&, ScalarGeom,
                                                const double*, double*, hipStream_t);
 template hipError_t launch_scalar_init<float>(const float*, Layout, Halo<float>, const FieldsArgs&, ScalarGeom,

@@ -495,7 +495,8 @@ class Lattice:
     def scalar_wall_flux(self) -> tuple[np.ndarray, np.ndarray]:
         """(bottom, top), [nx] each: the net amount of C that entered every column through the wall below row 0 /
         above the top row during the last substep (iblb_get_scalar_wall_flux); exact zeros at a no-flux wall, or
-        the source's wall_flux there once `set_scalar_source` gave one."""
+        the source's wall_flux there once `set_scalar_source` gave one.  The loss of `set_scalar_uptake` at a no-flux
+        wall is not in it: `scalar_uptake()["last"]` is the full net."""
         bottom, top = np.empty(self.x_count), np.empty(self.x_count)
         self._check(self._lib.iblb_get_scalar_wall_flux(self._h, _ptr(bottom), _ptr(top)))
         return bottom, top
@@ -544,6 +545,46 @@ class Lattice:
         out = np.empty((self.ny, self.x_count))
         self._check(self._lib.iblb_get_scalar_source(self._h, _ptr(out)))
         return out
+
+    def set_scalar_uptake(self, rate=(None, None)) -> None:
+        """First-order uptake at the no-flux walls and per-column accumulators of what crossed each wall, from the
+        next substep on (iblb_set_scalar_uptake).  rate: (below row 0, above the top row), [nx] each or None: the
+        flux out of a column is rate * C at the wall, per substep; only at walls of kind L.SCALAR_WALL_NOFLUX.  With
+        both None the uptake only accumulates.  Needs a scalar; replaces any previous uptake and zeroes its totals."""
+        def arr(a):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.size != self.x_count:
+                raise ValueError(f"expected {self.x_count} values, got {a.size}")
+            return a
+        r0, r1 = (arr(a) for a in rate)
+        up = L.ScalarUptake((C.c_void_p * 2)(_addr(r0), _addr(r1)))
+        self._check(self._lib.iblb_set_scalar_uptake(self._h, C.byref(up)))
+
+    def remove_scalar_uptake(self) -> None:
+        """Remove the uptake: the scalar's substep is then exactly what it is without one."""
+        self._check(self._lib.iblb_set_scalar_uptake(self._h, None))
+
+    def reset_scalar_uptake(self) -> None:
+        """Zero the uptake's totals, last and substeps; the rates stay (iblb_reset_scalar_uptake)."""
+        self._check(self._lib.iblb_reset_scalar_uptake(self._h))
+
+    def scalar_uptake(self) -> dict:
+        """{"total": (bottom, top), "last": (bottom, top), "substeps": n} (iblb_get_scalar_uptake), [nx] each: the
+        net amount of C that entered every column through the wall below row 0 / above the top row since the set or
+        the reset, and during the last substep (negative: absorbed)."""
+        out = [np.empty(self.x_count) for _ in range(4)]
+        n = C.c_longlong(0)
+        self._check(self._lib.iblb_get_scalar_uptake(self._h, *(_ptr(a) for a in out), C.byref(n)))
+        return {"total": (out[0], out[1]), "last": (out[2], out[3]), "substeps": n.value}
+
+    def scalar_uptake_info(self) -> dict:
+        """{"present", "substeps"} of the uptake (iblb_scalar_uptake_info); present: L.SCALAR_UPTAKE_* bits, 0: none
+        set."""
+        m, n = C.c_uint(0), C.c_longlong(0)
+        self._check(self._lib.iblb_scalar_uptake_info(self._h, C.byref(m), C.byref(n)))
+        return {"present": m.value, "substeps": n.value}
 
     @property
     def steps(self) -> int:

@@ -538,6 +538,53 @@ int iblb_set_scalar_source(iblb_ctx* ctx, const iblb_scalar_source* src);
 int iblb_scalar_source_info(iblb_ctx* ctx, double* decay, unsigned* present);
 int iblb_get_scalar_source(iblb_ctx* ctx, double* source);
 
+/* The scalar's uptake: first-order absorption at the no-flux walls (a reactive wall: the flux out of a column is its
+ * rate times C at the wall), and per-column accumulators of what crossed each wall, whatever the wall's kind, updated
+ * by every substep on the device.  It costs no readback and keeps the deep sweep; with no uptake set nothing changes. */
+typedef struct iblb_scalar_uptake {
+    const double* rate[2];   /* [XDIM] each, only where the scalar's wall kind is _NOFLUX: k[x], finite, >= 0,
+                                flux out of column x = k[x] * C at the wall, per substep; NULL = 0 */
+} iblb_scalar_uptake;        /* [0]: wall below row 0, [1]: wall above row YDIM-1 */
+/* iblb_set_scalar_uptake needs a scalar (IBLB_ERR_STATE otherwise; that covers the slabs of a group, which cannot
+ * hold one).  It copies its arrays to the device, replaces any previous uptake and takes effect from the next
+ * substep that runs; it moves neither t0 nor the event count.  up == NULL removes the uptake.  A struct with both
+ * rates NULL is valid: it only accumulates.  A rate entry that is not finite or is negative, rate[k] given for a
+ * _VALUE wall: IBLB_ERR_ARG, checked before anything is touched.  The new device buffers are allocated before the old
+ * ones are freed: any error, IBLB_ERR_NOMEM included, leaves the previous uptake (rates, totals, substeps) as it
+ * was.  A successful set, a replacement included, starts total, last and substeps at zero.
+ * Update rule.  On the host, once per set (every operation in double, rounded once, no contraction):
+ *   a_k[x] = 2.0 - 2.0/(1.0 + 3.0*rate[k][x])                 0.0 where rate[k] is NULL
+ * With an uptake set, one substep replaces the wall line of the rule in force (that of iblb_set_scalar, or of
+ * iblb_set_scalar_source when a source is set) by the following, for the wall below row 0; the wall above the top row
+ * likewise with p_3(x, YDIM-1), g_4'(x, YDIM-1) and index [1].  q = p_4(x, 0), the relaxed population of the rule in
+ * force (with the source's w_i*r term when a source is set); e = wall_flux[0][x] of a set source, else 0.0:
+ *   _NOFLUX:  l = a_0[x]*q;   g_3'(x, 0) = (q - l) + e;   net = e - l
+ *   _VALUE:   g_3'(x, 0) as the rule in force (unchanged);   net = g_3'(x, 0) - q
+ *   total[0][x] = total[0][x] + net;   last[0][x] = net;   substeps = substeps + 1 (once per substep)
+ * Every operation in double, rounded once, no contraction; no term is skipped for a NULL array, so results are pinned
+ * by value (==); the sign of a zero is not part of the contract.  net is what entered column x through that wall
+ * during the substep (negative: left).  Halfway anti-bounce-back gives p_4 + g_3' = 2 w1 C_w; with g_3' = (1 - a) p_4
+ * the loss a p_4 equals k C_w for a = 6k/(1 + 3k) = 2 - 2/(1 + 3k): a runs from 0 (the no-flux wall) to 2 as k grows,
+ * and a = 2 is exactly the _VALUE wall at 0.0.  The steady state between such a wall and a _VALUE wall is exact.
+ * Between walls that are not _VALUE and with no bulk source or decay, sum(C) changes per substep by
+ * sum_x(net bottom + net top), up to rounding.  An event of `stride` substeps adds every one of them; each entry has
+ * one writer per substep and the substeps are ordered, so the sums are reproducible bit for bit.
+ * iblb_get_scalar_wall_flux keeps its stated expressions under an uptake: at a _NOFLUX wall it returns the prescribed
+ * flux (or 0.0) and does not contain the uptake loss; last_bottom / last_top below are the full net.
+ * iblb_get_scalar_uptake returns total and last of both walls, [XDIM] each, and the substeps accumulated; any pointer
+ * may be NULL, not all five (IBLB_ERR_ARG).  iblb_reset_scalar_uptake zeroes total, last and substeps and keeps the
+ * rates.  No uptake set: IBLB_ERR_STATE from both.
+ * iblb_scalar_uptake_info (either pointer may be NULL): present = 1 (an uptake is set) | 2, 4 (rate[0], rate[1]), and
+ * substeps; none set: 0 and 0.
+ * iblb_set_scalar removes the uptake with the scalar it belonged to, whether it replaces or removes the scalar.
+ * iblb_set_scalar_source keeps the uptake and its totals, setting or removing the source.  iblb_set_state keeps it,
+ * iblb_load_checkpoint removes it along with the scalar (checkpoints hold no uptake), iblb_destroy frees it. */
+int iblb_set_scalar_uptake(iblb_ctx* ctx, const iblb_scalar_uptake* up);
+int iblb_get_scalar_uptake(iblb_ctx* ctx, double* total_bottom, double* total_top, double* last_bottom,
+                           double* last_top, long long* substeps);
+int iblb_reset_scalar_uptake(iblb_ctx* ctx);
+int iblb_scalar_uptake_info(iblb_ctx* ctx, unsigned* present, long long* substeps);
+
 /* Timing: when enabled (1) every collide-stream launch is bracketed by HIP events on the
  * stream it runs on; iblb_get_timing() returns the sums (and resets them if reset).  enabled = 2:
  * only the deep (K-iteration) launches are timed, by their own dispatch / completion signals (no
