@@ -125,6 +125,22 @@ class ScalarUptake(C.Structure):
 SCALAR_UPTAKE_SET = 1
 SCALAR_UPTAKE_RATE = (2, 4)
 
+# end kinds of iblb_set_scalar_ends
+SCALAR_END_NOFLUX = 0
+SCALAR_END_VALUE = 1
+SCALAR_END_OUTFLOW = 2
+SCALAR_END_KINDS = {"noflux": SCALAR_END_NOFLUX, "value": SCALAR_END_VALUE, "outflow": SCALAR_END_OUTFLOW}
+
+
+class ScalarEnds(C.Structure):
+    """struct iblb_scalar_ends (include/iblb.h)."""
+    _fields_ = [("kind", C.c_int * 2), ("value", C.c_double * 2), ("profile", C.c_void_p * 2)]
+
+
+# the `present` bits of iblb_scalar_ends_info
+SCALAR_ENDS_SET = 1
+SCALAR_ENDS_PROFILE = (2, 4)
+
 
 class FieldStats(C.Structure):
     """struct iblb_field_stats (include/iblb.h)."""
@@ -195,6 +211,11 @@ _SIGS = {
     "iblb_get_scalar_uptake": ([_vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_longlong)], C.c_int),
     "iblb_reset_scalar_uptake": ([_vp], C.c_int),
     "iblb_scalar_uptake_info": ([_vp, C.POINTER(C.c_uint), C.POINTER(C.c_longlong)], C.c_int),
+    "iblb_set_scalar_ends": ([_vp, C.POINTER(ScalarEnds)], C.c_int),
+    "iblb_get_scalar_ends": ([_vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_longlong)], C.c_int),
+    "iblb_reset_scalar_ends": ([_vp], C.c_int),
+    "iblb_scalar_ends_info": ([_vp, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_uint),
+                               C.POINTER(C.c_longlong)], C.c_int),
     "iblb_set_profiling": ([_vp, C.c_int], C.c_int),
     "iblb_get_timing": ([_vp, C.POINTER(Timing), C.c_int], C.c_int),
     "iblb_get_timing_ex": ([_vp, C.POINTER(Timing), C.c_ulong, C.c_int], C.c_int),

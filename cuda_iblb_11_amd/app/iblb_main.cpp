@@ -51,6 +51,12 @@
 // >= 0.  At every output iteration <it>-uptake.dat beside <it>-scalar.dat holds one line per column (%.17g),
 //   x  total_bottom  total_top
 // the net amount of C that entered the column through each wall since the run's first iteration (negative: absorbed).
+// IBLB_SCALAR_ENDS=left,right[,value_left[,value_right]] (needs IBLB_SCALAR) opens that scalar's ends in x
+// (iblb_set_scalar_ends): left and right in noflux|value|outflow, the values (finite, default 0) for the ends of kind
+// `value`; the fluid stays periodic.  At every output iteration <it>-ends.dat beside <it>-scalar.dat holds one line
+// per row (%.17g),
+//   y  total_left  total_right
+// the net amount of C that entered the row through each end since the run's first iteration (negative: it left).
 #include <sys/stat.h>
 #include <sys/time.h>
 #include <unistd.h>
@@ -358,6 +364,46 @@ int main(int argc, char* argv[]) {
         sc_uptake = true;
     }
 
+    // the scalar's open ends in x (extension): a kind per end and a uniform value for an end of kind `value`
+    bool sc_ends = false;
+    int sc_end_kind[2] = {IBLB_SCALAR_END_NOFLUX, IBLB_SCALAR_END_NOFLUX};
+    double sc_end_value[2] = {0., 0.};
+    if (const char* ss = getenv("IBLB_SCALAR_ENDS"); ss && *ss) {
+        // two kinds and at most two finite numbers, separated by commas, nothing else
+        std::vector<std::string> parts(1);
+        for (const char* p = ss; *p; ++p) {
+            if (*p == ',') parts.emplace_back();
+            else parts.back() += *p;
+        }
+        bool ok = parts.size() >= 2 && parts.size() <= 4;
+        for (size_t n = 0; ok && n < 2; ++n) {
+            if (parts[n] == "noflux") sc_end_kind[n] = IBLB_SCALAR_END_NOFLUX;
+            else if (parts[n] == "value") sc_end_kind[n] = IBLB_SCALAR_END_VALUE;
+            else if (parts[n] == "outflow") sc_end_kind[n] = IBLB_SCALAR_END_OUTFLOW;
+            else ok = false;
+        }
+        for (size_t n = 2; ok && n < parts.size(); ++n) {
+            const char* p = parts[n].c_str();
+            char* end = nullptr;
+            errno = 0;
+            const double v = strtod(p, &end);
+            ok = ((*p >= '0' && *p <= '9') || *p == '.' || *p == '+' || *p == '-') && end != p && *end == 0 &&
+                 errno == 0 && std::isfinite(v);
+            sc_end_value[n - 2] = v;
+        }
+        if (!ok) {
+            if (lead)
+                cerr << "IBLB_SCALAR_ENDS must be left,right[,value_left[,value_right]] with left and right in "
+                        "noflux|value|outflow and finite values, got " << ss << endl;
+            return 2;
+        }
+        if (!(sc_tau > 0.)) {
+            if (lead) cerr << "IBLB_SCALAR_ENDS needs IBLB_SCALAR: there is no scalar to open" << endl;
+            return 2;
+        }
+        sc_ends = true;
+    }
+
     const double dx = 1. / LENGTH;
     const double dt = 1. / (T);
     const double SPEED = 0.8 * 1000 / T;
@@ -456,6 +502,8 @@ int main(int argc, char* argv[]) {
     std::vector<double> sc_out(sc_tau > 0. ? (size_t)sc_win.nx * sc_win.ny : 0);
     std::vector<double> up_total[2];
     for (auto& v : up_total) v.assign(sc_uptake ? (size_t)XDIM : 0, 0.);
+    std::vector<double> end_total[2];
+    for (auto& v : end_total) v.assign(sc_ends ? (size_t)YDIM : 0, 0.);
     if (sc_tau > 0.) {
         std::vector<double> c0((size_t)size);
         for (int j = 0; j < size; j++) c0[j] = (unsigned int)j / XDIM < YDIM / 2 ? 1. : 0.;
@@ -470,6 +518,14 @@ int main(int argc, char* argv[]) {
             const std::vector<double> k0((size_t)XDIM, sc_rate[0]), k1((size_t)XDIM, sc_rate[1]);
             const iblb_scalar_uptake up{{k0.data(), k1.data()}};
             if ((rc = iblb_set_scalar_uptake(ctx, &up))) return die(ctx, rc, "iblb_set_scalar_uptake");
+        }
+        if (sc_ends) {
+            // a value given for an end of another kind is not used
+            const iblb_scalar_ends ends{{sc_end_kind[0], sc_end_kind[1]},
+                                        {sc_end_kind[0] == IBLB_SCALAR_END_VALUE ? sc_end_value[0] : 0.,
+                                         sc_end_kind[1] == IBLB_SCALAR_END_VALUE ? sc_end_value[1] : 0.},
+                                        {nullptr, nullptr}};
+            if ((rc = iblb_set_scalar_ends(ctx, &ends))) return die(ctx, rc, "iblb_set_scalar_ends");
         }
     }
 
@@ -689,6 +745,19 @@ int main(int argc, char* argv[]) {
                 for (size_t i = 0; i < (size_t)XDIM; i++)
                     fprintf(fu, "%zu\t%.17g\t%.17g\n", i, up_total[0][i], up_total[1][i]);
                 fclose(fu);
+            }
+            if (sc_ends) {
+                if ((rc = iblb_get_scalar_ends(ctx, end_total[0].data(), end_total[1].data(), nullptr, nullptr, nullptr)))
+                    return die(ctx, rc, "iblb_get_scalar_ends");
+                outfile = raw_data + to_string(it) + "-ends.dat";
+                FILE* fe = fopen(outfile.c_str(), "w");
+                if (!fe) {
+                    fprintf(stderr, "cannot write %s: %s\n", outfile.c_str(), strerror(errno));
+                    return 1;
+                }
+                for (size_t j = 0; j < (size_t)YDIM; j++)
+                    fprintf(fe, "%zu\t%.17g\t%.17g\n", j, end_total[0][j], end_total[1][j]);
+                fclose(fe);
             }
             if (av_stride > 0 && !av_first) {
                 outfile = raw_data + to_string(it) + "-mean.dat";

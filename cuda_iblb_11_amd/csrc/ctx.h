@@ -232,6 +232,14 @@ struct iblb_ctx {
     double* sc_up = nullptr;
     unsigned sc_up_present = 0;   // the `present` bits of iblb_scalar_uptake_info
     long long sc_up_substeps = 0; // substeps accumulated since the set / the reset
+    // the scalar's open ends in x (iblb_set_scalar_ends).  sc_end_present == 0: none, the scalar is periodic.  sc_end:
+    // one allocation of [6 * ny], value, total, last of ScalarEnds ([2 * ny] each, the left end then the right one); a
+    // NULL profile of the call is held as the uniform value.  Lives and dies with the scalar.
+    double* sc_end = nullptr;
+    int sc_end_kind[2] = {0, 0};
+    double sc_end_value[2] = {0.0, 0.0};  // as given
+    unsigned sc_end_present = 0;   // the `present` bits of iblb_scalar_ends_info
+    long long sc_end_substeps = 0; // substeps accumulated since the set / the reset
     // state machine
     int phase = iblbh::PH_EMPTY;
     long long t = 0;

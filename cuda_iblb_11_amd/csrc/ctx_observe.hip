@@ -26,9 +26,19 @@ static void scalar_uptake_free(iblb_ctx* c) {
     c->sc_up_substeps = 0;
 }
 
+static void scalar_ends_free(iblb_ctx* c) {
+    if (c->sc_end) (void)hipFree(c->sc_end);
+    c->sc_end = nullptr;
+    c->sc_end_kind[0] = c->sc_end_kind[1] = 0;
+    c->sc_end_value[0] = c->sc_end_value[1] = 0.0;
+    c->sc_end_present = 0;
+    c->sc_end_substeps = 0;
+}
+
 void scalar_free(iblb_ctx* c) {
     scalar_source_free(c);  // the source belongs to the scalar it was set on
     scalar_uptake_free(c);  // and so does the uptake
+    scalar_ends_free(c);    // and the open ends
     if (c->sc_alloc) (void)hipFree(c->sc_alloc);
     c->sc_alloc = c->sc_g[0] = c->sc_g[1] = c->sc_uv = nullptr;
     c->sc_cur = 0;
@@ -54,6 +64,13 @@ static ScalarUptake scalar_uptake(const iblb_ctx* c) {
     if (!c->sc_up) return ScalarUptake{nullptr, nullptr, nullptr};
     const size_t n = 2 * (size_t)c->ncol;
     return ScalarUptake{c->sc_up, c->sc_up + n, c->sc_up + 2 * n};
+}
+
+// nullptr members without open ends: the launchers then run the builds without them
+static ScalarEnds scalar_ends(const iblb_ctx* c) {
+    if (!c->sc_end) return ScalarEnds{{0, 0}, nullptr, nullptr, nullptr};
+    const size_t n = 2 * (size_t)c->ny;
+    return ScalarEnds{{c->sc_end_kind[0], c->sc_end_kind[1]}, c->sc_end, c->sc_end + n, c->sc_end + 2 * n};
 }
 
 void tracers_free(iblb_ctx* c) {
@@ -117,7 +134,8 @@ static int average_update(iblb_ctx* c) {
 // joined, the owed IB force evaluated), then `stride` substeps with the velocity of this state: the first
 // evaluates it from the fluid populations and leaves it in the scratch, the others read the scratch.  With a source
 // (iblb_set_scalar_source) every substep runs the SOURCE build, without one the build that has none; likewise the
-// UPTAKE builds with an uptake (iblb_set_scalar_uptake), whose accumulators then take every substep of the event.
+// UPTAKE builds with an uptake (iblb_set_scalar_uptake), whose accumulators then take every substep of the event, and
+// the ENDS builds with open ends (iblb_set_scalar_ends).
 static int scalar_update(iblb_ctx* c) {
     if (!single_slab(c))  // the context joined a group after iblb_set_scalar: its lattice is the whole lattice's
         return fail(c, IBLB_ERR_UNSUPPORTED, "scalar: a lone slab only; remove it before joining a group");
@@ -128,17 +146,19 @@ static int scalar_update(iblb_ctx* c) {
     const ScalarRule R = scalar_rule(c->sc_cfg);
     const ScalarSource Q = scalar_source(c);
     const ScalarUptake U = scalar_uptake(c);
+    const ScalarEnds E = scalar_ends(c);
     HIP_TRY(c, with_state(c, [&](auto* g, auto H) {
-        return launch_scalar_first(g, c->L, H, a, S, R, Q, U, c->sc_g[c->sc_cur], c->sc_g[c->sc_cur ^ 1], c->sc_uv,
+        return launch_scalar_first(g, c->L, H, a, S, R, Q, U, E, c->sc_g[c->sc_cur], c->sc_g[c->sc_cur ^ 1], c->sc_uv,
                                    c->stream);
     }));
     c->sc_cur ^= 1;
     for (int k = 1; k < c->sc_ev.stride; ++k) {
-        HIP_TRY(c, launch_scalar_next(S, R, Q, U, c->sc_g[c->sc_cur], c->sc_g[c->sc_cur ^ 1], c->sc_uv, c->stream));
+        HIP_TRY(c, launch_scalar_next(S, R, Q, U, E, c->sc_g[c->sc_cur], c->sc_g[c->sc_cur ^ 1], c->sc_uv, c->stream));
         c->sc_cur ^= 1;
     }
     c->sc_ev.advance();
     if (c->sc_up) c->sc_up_substeps += c->sc_ev.stride;
+    if (c->sc_end) c->sc_end_substeps += c->sc_ev.stride;
     return IBLB_OK;
 }
 
@@ -603,6 +623,101 @@ int iblb_scalar_uptake_info(iblb_ctx* c, unsigned* present, long long* substeps)
     if (!c) return IBLB_ERR_ARG;
     if (present) *present = c->sc_up_present;
     if (substeps) *substeps = c->sc_up_substeps;
+    return IBLB_OK;
+}
+
+// ---- the scalar's open ends in x ----------------------------------------------------------------------
+int iblb_set_scalar_ends(iblb_ctx* c, const iblb_scalar_ends* ends) {
+    if (!c) return IBLB_ERR_ARG;
+    if (!c->sc_alloc)
+        return fail(c, IBLB_ERR_STATE, single_slab(c) ? "iblb_set_scalar_ends: no scalar is set (iblb_set_scalar)"
+                                                      : "iblb_set_scalar_ends: a slab of a group holds no scalar");
+    const size_t ny = (size_t)c->ny;
+    if (ends) {
+        for (int k = 0; k < 2; ++k) {
+            const int kind = ends->kind[k];
+            if (kind != IBLB_SCALAR_END_NOFLUX && kind != IBLB_SCALAR_END_VALUE && kind != IBLB_SCALAR_END_OUTFLOW)
+                return fail(c, IBLB_ERR_ARG, "kind is none of IBLB_SCALAR_END_NOFLUX, _VALUE, _OUTFLOW");
+            if (kind != IBLB_SCALAR_END_VALUE) {
+                if (ends->profile[k])
+                    return fail(c, IBLB_ERR_ARG, "profile is given for an end that is not of kind IBLB_SCALAR_END_VALUE");
+                continue;
+            }
+            if (!std::isfinite(ends->value[k])) return fail(c, IBLB_ERR_ARG, "value of a _VALUE end is not finite");
+            if (ends->profile[k] && !all_finite(ends->profile[k], ny))
+                return fail(c, IBLB_ERR_ARG, "profile holds an entry that is not finite");
+        }
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (!ends) {
+        scalar_ends_free(c);
+        return IBLB_OK;
+    }
+    // value, total, last side by side; a NULL profile is the uniform value (0.0 at an end that takes none), and both
+    // accumulators start as zeros
+    std::vector<double> host(6 * ny, 0.0);
+    unsigned present = 1u;
+    for (int k = 0; k < 2; ++k) {
+        if (ends->kind[k] != IBLB_SCALAR_END_VALUE) continue;
+        for (size_t y = 0; y < ny; ++y) host[(size_t)k * ny + y] = ends->profile[k] ? ends->profile[k][y] : ends->value[k];
+        if (ends->profile[k]) present |= 2u << k;
+    }
+    // the new buffer first: a failed allocation leaves the previous ends as they were
+    DevBuf d;
+    HIP_TRY(c, hipMalloc(&d.p, 6 * ny * sizeof(double)));
+    HIP_TRY(c, hipMemcpyAsync(d.p, host.data(), 6 * ny * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    scalar_ends_free(c);
+    c->sc_end = (double*)d.p;
+    d.p = nullptr;
+    for (int k = 0; k < 2; ++k) {
+        c->sc_end_kind[k] = ends->kind[k];
+        c->sc_end_value[k] = ends->value[k];
+    }
+    c->sc_end_present = present;
+    return IBLB_OK;
+}
+
+int iblb_reset_scalar_ends(iblb_ctx* c) {
+    if (!c) return IBLB_ERR_ARG;
+    if (!c->sc_end) return fail(c, IBLB_ERR_STATE, "iblb_reset_scalar_ends: no ends are set");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n = 2 * (size_t)c->ny;  // total and last follow value
+    HIP_TRY(c, hipMemsetAsync(c->sc_end + n, 0, 2 * n * sizeof(double), c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->sc_end_substeps = 0;
+    return IBLB_OK;
+}
+
+int iblb_get_scalar_ends(iblb_ctx* c, double* total_left, double* total_right, double* last_left, double* last_right,
+                         long long* substeps) {
+    if (!c) return IBLB_ERR_ARG;
+    if (!c->sc_end) return fail(c, IBLB_ERR_STATE, "iblb_get_scalar_ends: no ends are set");
+    if (!total_left && !total_right && !last_left && !last_right && !substeps)
+        return fail(c, IBLB_ERR_ARG, "every output is NULL");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const ScalarEnds E = scalar_ends(c);
+    const size_t nb = (size_t)c->ny * sizeof(double);
+    int rc = read_back(c, {{total_left, E.total, nb},
+                           {total_right, E.total + c->ny, nb},
+                           {last_left, E.last, nb},
+                           {last_right, E.last + c->ny, nb}});
+    if (rc) return rc;
+    if (substeps) *substeps = c->sc_end_substeps;
+    return IBLB_OK;
+}
+
+int iblb_scalar_ends_info(iblb_ctx* c, int kind[2], double value[2], unsigned* present, long long* substeps) {
+    if (!c) return IBLB_ERR_ARG;
+    if (c->sc_end_present) {
+        for (int k = 0; k < 2; ++k) {
+            if (kind) kind[k] = c->sc_end_kind[k];
+            if (value) value[k] = c->sc_end_value[k];
+        }
+    }
+    if (present) *present = c->sc_end_present;
+    if (substeps) *substeps = c->sc_end_substeps;
     return IBLB_OK;
 }
 

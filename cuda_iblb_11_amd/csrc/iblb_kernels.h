@@ -290,15 +290,26 @@ struct ScalarUptake {
     double* total;    // what crossed wall k of column x since the set / the reset
     double* last;     // ... during the last substep
 };
+// The scalar's open ends in x (include/iblb.h iblb_set_scalar_ends).  value == nullptr: none (the scalar is periodic
+// in x), and every launch below runs the build without them.  Otherwise all three arrays are set, [2 * ny] each, index
+// k * ny + y for end k (0: left of column 0, 1: right of column ncol - 1): a NULL profile of the ABI is held as an
+// array of the uniform value, so that the kernels have no per-pointer branch.
+struct ScalarEnds {
+    int kind[2];          // IBLB_SCALAR_END_*
+    const double* value;  // the value of row y at a _VALUE end
+    double* total;        // what crossed end k in row y since the set / the reset
+    double* last;         // ... during the last substep
+};
 // One substep src -> dst (distinct buffers).  first: the velocity from the fluid state by cell_state of
 // field_eval.h (of FieldsArgs the window members are unused), also left in uv; next: the velocity read from uv.
-// With an uptake the lanes of rows 0 and ny - 1 also update U.total and U.last, one writer per entry.
+// With an uptake the lanes of rows 0 and ny - 1 also update U.total and U.last, one writer per entry; with open ends
+// the lanes of columns 0 and ncol - 1 likewise E.total and E.last.
 template <typename T>
 hipError_t launch_scalar_first(const T* f, Layout L, Halo<T> H, const FieldsArgs& a, ScalarGeom S, ScalarRule R,
-                               ScalarSource Q, ScalarUptake U, const double* src, double* dst, double* uv,
-                               hipStream_t s);
-hipError_t launch_scalar_next(ScalarGeom S, ScalarRule R, ScalarSource Q, ScalarUptake U, const double* src,
-                              double* dst, const double* uv, hipStream_t s);
+                               ScalarSource Q, ScalarUptake U, ScalarEnds E, const double* src, double* dst,
+                               double* uv, hipStream_t s);
+hipError_t launch_scalar_next(ScalarGeom S, ScalarRule R, ScalarSource Q, ScalarUptake U, ScalarEnds E,
+                              const double* src, double* dst, const double* uv, hipStream_t s);
 // dst's five planes = the equilibrium of C = c[x * rows + y] at the fluid state's velocity; c may be dst's plane 0.
 template <typename T>
 hipError_t launch_scalar_init(const T* f, Layout L, Halo<T> H, const FieldsArgs& a, ScalarGeom S, const double* c,

@@ -26,6 +26,14 @@
 // scalar_wall_flux_kernel, 2 / ny of a substep's traffic.  Every entry has one writer per substep (with ny == 1 one
 // lane writes both walls' entries) and successive substeps are ordered by the stream: no atomics, and the sums are
 // bit-reproducible.  Without an uptake the builds without UPTAKE run: the kernels as they were.
+// With open ends (iblb_set_scalar_ends) the ENDS builds run: x does not wrap.  The lanes of column 0 store what
+// g_1'(0, y) receives by the left end's kind instead of pushing p_2 to column ncol - 1, those of column ncol - 1
+// likewise for g_2' and p_1: the map stays a bijection of (cell, direction), and with D2Q5 an end rule and a wall
+// rule never concern the same direction.  x = blockIdx.x, so the end test is uniform over the workgroup.  An end lane
+// loads its row's value and running total from the ends' arrays ([2 * ny] each, index k * ny + y) and stores the
+// total and the substep's net amount: these accesses run along y with the lanes, contiguous like the planes'.  One
+// writer per entry per substep (with ncol == 1 one lane writes both ends' entries), no atomics.  Without ends the
+// builds without ENDS run: the kernels as they were.
 //
 // The transposes between the ABI's layouts ([y * nx + x]) and the device's go through an LDS tile so that both
 // sides coalesce.
@@ -58,14 +66,30 @@ __device__ __forceinline__ double uptake_wall(double q, double e, bool value, co
     return out;
 }
 
+// One end lane's store under open ends (include/iblb.h iblb_set_scalar_ends).  q: the population that would leave
+// through end k; own: the cell's relaxed population of the opposite direction (what its inner neighbour receives);
+// w: the row's index into the ends' arrays.  Returns what the opposite direction of the same cell receives, and adds
+// the net amount that entered to the row's total.
+__device__ __forceinline__ double end_cell(double q, double own, const ScalarEnds& E, int k, long w) {
+#pragma clang fp contract(off)
+    double out = q;
+    if (E.kind[k] == IBLB_SCALAR_END_VALUE) out = (2.0 * SW1) * E.value[w] - q;
+    else if (E.kind[k] == IBLB_SCALAR_END_OUTFLOW) out = own;
+    const double net = out - q;
+    E.total[w] = E.total[w] + net;
+    E.last[w] = net;
+    return out;
+}
+
 // One cell of a substep: g[5] of cell (x, y) relaxed towards the equilibrium at (ux, uy) and pushed into dst.
 // SOURCE: the rule of iblb_set_scalar_source.  sv = s(x, y) of the lane's cell; the lanes of rows 0 and ny - 1 load
 // their column's one wall entry (the flux or the value, by the wall's kind) from Q.walls.
 // UPTAKE: the rule of iblb_set_scalar_uptake at those two rows, with or without a source.
-template <bool SOURCE, bool UPTAKE>
+// ENDS: the rule of iblb_set_scalar_ends at columns 0 and ncol - 1 for the directions 1 and 2; nothing wraps.
+template <bool SOURCE, bool UPTAKE, bool ENDS>
 __device__ __forceinline__ void scalar_push(const double g[5], double ux, double uy, const ScalarGeom& S,
                                             const ScalarRule& R, const ScalarSource& Q, const ScalarUptake& U,
-                                            double sv, int x, int y, double* __restrict__ dst) {
+                                            const ScalarEnds& E, double sv, int x, int y, double* __restrict__ dst) {
 #pragma clang fp contract(off)
     const double C = (((g[0] + g[1]) + g[2]) + g[3]) + g[4];
     const double a[5] = {0.0, ux, -ux, uy, -uy};
@@ -82,11 +106,18 @@ __device__ __forceinline__ void scalar_push(const double g[5], double ux, double
         if constexpr (SOURCE) p[i] = p[i] + (i == 0 ? SW0 : SW1) * r;
     }
     const long o = (long)x * S.rows + y;
-    const long oxp = (long)(x + 1 < S.ncol ? x + 1 : 0) * S.rows + y;
-    const long oxm = (long)(x > 0 ? x - 1 : S.ncol - 1) * S.rows + y;
     dst[o] = p[0];
-    dst[S.plane + oxp] = p[1];
-    dst[2 * S.plane + oxm] = p[2];
+    if constexpr (ENDS) {
+        if (x + 1 < S.ncol) dst[S.plane + o + S.rows] = p[1];
+        else dst[2 * S.plane + o] = end_cell(p[1], p[2], E, 1, (long)S.ny + y);
+        if (x > 0) dst[2 * S.plane + o - S.rows] = p[2];
+        else dst[S.plane + o] = end_cell(p[2], p[1], E, 0, (long)y);
+    } else {
+        const long oxp = (long)(x + 1 < S.ncol ? x + 1 : 0) * S.rows + y;
+        const long oxm = (long)(x > 0 ? x - 1 : S.ncol - 1) * S.rows + y;
+        dst[S.plane + oxp] = p[1];
+        dst[2 * S.plane + oxm] = p[2];
+    }
     if constexpr (UPTAKE) {
         if (y + 1 < S.ny) dst[3 * S.plane + o + 1] = p[3];
         else {
@@ -124,12 +155,13 @@ __device__ __forceinline__ void scalar_push(const double g[5], double ux, double
 }
 
 // grid: (ncol, ceil(ny / 256)); one lane per cell.  The SOURCE builds load one more plane, Q.field; the others
-// never touch Q.  U stands last: the builds without UPTAKE never touch it, and their other arguments keep their places.
-template <typename T, bool SOURCE, bool UPTAKE>
+// never touch Q.  U and then E stand last: the builds without UPTAKE / ENDS never touch them, and their other
+// arguments keep their places.
+template <typename T, bool SOURCE, bool UPTAKE, bool ENDS>
 __global__ __launch_bounds__(256) void scalar_first_kernel(const T* __restrict__ f, Layout L, Halo<T> H, FieldsArgs a,
                                                            ScalarGeom S, ScalarRule R, ScalarSource Q,
                                                            const double* __restrict__ src, double* __restrict__ dst,
-                                                           double* __restrict__ uv, ScalarUptake U) {
+                                                           double* __restrict__ uv, ScalarUptake U, ScalarEnds E) {
     const int x = blockIdx.x, y = blockIdx.y * 256 + threadIdx.x;
     if (x >= S.ncol || y >= S.ny) return;
     const long o = (long)x * S.rows + y;
@@ -140,13 +172,14 @@ __global__ __launch_bounds__(256) void scalar_first_kernel(const T* __restrict__
     cell_state<T>(f, L, H, a, x, y, pop, r, ux, uy);
     uv[o] = ux;
     uv[S.plane + o] = uy;
-    scalar_push<SOURCE, UPTAKE>(g, ux, uy, S, R, Q, U, sv, x, y, dst);
+    scalar_push<SOURCE, UPTAKE, ENDS>(g, ux, uy, S, R, Q, U, E, sv, x, y, dst);
 }
 
-template <bool SOURCE, bool UPTAKE>
+template <bool SOURCE, bool UPTAKE, bool ENDS>
 __global__ __launch_bounds__(256) void scalar_next_kernel(ScalarGeom S, ScalarRule R, ScalarSource Q,
                                                           const double* __restrict__ src, double* __restrict__ dst,
-                                                          const double* __restrict__ uv, ScalarUptake U) {
+                                                          const double* __restrict__ uv, ScalarUptake U,
+                                                          ScalarEnds E) {
     const int x = blockIdx.x, y = blockIdx.y * 256 + threadIdx.x;
     if (x >= S.ncol || y >= S.ny) return;
     const long o = (long)x * S.rows + y;
@@ -154,7 +187,7 @@ __global__ __launch_bounds__(256) void scalar_next_kernel(ScalarGeom S, ScalarRu
 #pragma unroll
     for (int i = 0; i < 5; ++i) g[i] = src[i * S.plane + o];
     if constexpr (SOURCE) sv = Q.field[o];
-    scalar_push<SOURCE, UPTAKE>(g, uv[o], uv[S.plane + o], S, R, Q, U, sv, x, y, dst);
+    scalar_push<SOURCE, UPTAKE, ENDS>(g, uv[o], uv[S.plane + o], S, R, Q, U, E, sv, x, y, dst);
 }
 
 // The equilibrium of C = c[x * rows + y] (device layout: plane 0 of dst's own transposed input) at the cell's
@@ -250,39 +283,65 @@ inline bool source_ok(const ScalarSource& Q) { return (Q.field != nullptr) == (Q
 inline bool uptake_ok(const ScalarUptake& U) {
     return (U.a != nullptr) == (U.total != nullptr) && (U.a != nullptr) == (U.last != nullptr);
 }
+// open ends have all three of their arrays or none, and kinds among the three
+inline bool ends_ok(const ScalarEnds& E) {
+    if ((E.value != nullptr) != (E.total != nullptr) || (E.value != nullptr) != (E.last != nullptr)) return false;
+    if (!E.value) return true;
+    for (int k = 0; k < 2; ++k)
+        if (E.kind[k] < IBLB_SCALAR_END_NOFLUX || E.kind[k] > IBLB_SCALAR_END_OUTFLOW) return false;
+    return true;
+}
 inline dim3 cell_grid(const ScalarGeom& S) { return dim3((unsigned)S.ncol, (unsigned)((S.ny + 255) / 256)); }
 inline dim3 tile_grid(int nx, int ny, int planes) {
     return dim3((unsigned)((ny + TILE - 1) / TILE), (unsigned)((nx + TILE - 1) / TILE), (unsigned)planes);
+}
+
+// the ENDS build or the one without, by E.value, under the SOURCE and UPTAKE the caller chose
+template <typename T, bool SOURCE, bool UPTAKE>
+void first_launch(dim3 grid, hipStream_t s, const T* f, Layout L, Halo<T> H, const FieldsArgs& a, ScalarGeom S,
+                  ScalarRule R, ScalarSource Q, const double* src, double* dst, double* uv, ScalarUptake U,
+                  ScalarEnds E) {
+    if (E.value)
+        scalar_first_kernel<T, SOURCE, UPTAKE, true><<<grid, 256, 0, s>>>(f, L, H, a, S, R, Q, src, dst, uv, U, E);
+    else scalar_first_kernel<T, SOURCE, UPTAKE, false><<<grid, 256, 0, s>>>(f, L, H, a, S, R, Q, src, dst, uv, U, E);
+}
+
+template <bool SOURCE, bool UPTAKE>
+void next_launch(dim3 grid, hipStream_t s, ScalarGeom S, ScalarRule R, ScalarSource Q, const double* src, double* dst,
+                 const double* uv, ScalarUptake U, ScalarEnds E) {
+    if (E.value) scalar_next_kernel<SOURCE, UPTAKE, true><<<grid, 256, 0, s>>>(S, R, Q, src, dst, uv, U, E);
+    else scalar_next_kernel<SOURCE, UPTAKE, false><<<grid, 256, 0, s>>>(S, R, Q, src, dst, uv, U, E);
 }
 
 }  // namespace
 
 template <typename T>
 hipError_t launch_scalar_first(const T* f, Layout L, Halo<T> H, const FieldsArgs& a, ScalarGeom S, ScalarRule R,
-                               ScalarSource Q, ScalarUptake U, const double* src, double* dst, double* uv,
-                               hipStream_t s) {
-    if (!geom_ok(S) || S.ncol != L.ncol || S.ny != L.ny || !source_ok(Q) || !uptake_ok(U)) return hipErrorInvalidValue;
+                               ScalarSource Q, ScalarUptake U, ScalarEnds E, const double* src, double* dst,
+                               double* uv, hipStream_t s) {
+    if (!geom_ok(S) || S.ncol != L.ncol || S.ny != L.ny || !source_ok(Q) || !uptake_ok(U) || !ends_ok(E))
+        return hipErrorInvalidValue;
     const dim3 grid = cell_grid(S);
     if (U.a) {
-        if (Q.field) scalar_first_kernel<T, true, true><<<grid, 256, 0, s>>>(f, L, H, a, S, R, Q, src, dst, uv, U);
-        else scalar_first_kernel<T, false, true><<<grid, 256, 0, s>>>(f, L, H, a, S, R, Q, src, dst, uv, U);
+        if (Q.field) first_launch<T, true, true>(grid, s, f, L, H, a, S, R, Q, src, dst, uv, U, E);
+        else first_launch<T, false, true>(grid, s, f, L, H, a, S, R, Q, src, dst, uv, U, E);
     } else {
-        if (Q.field) scalar_first_kernel<T, true, false><<<grid, 256, 0, s>>>(f, L, H, a, S, R, Q, src, dst, uv, U);
-        else scalar_first_kernel<T, false, false><<<grid, 256, 0, s>>>(f, L, H, a, S, R, Q, src, dst, uv, U);
+        if (Q.field) first_launch<T, true, false>(grid, s, f, L, H, a, S, R, Q, src, dst, uv, U, E);
+        else first_launch<T, false, false>(grid, s, f, L, H, a, S, R, Q, src, dst, uv, U, E);
     }
     return hipGetLastError();
 }
 
-hipError_t launch_scalar_next(ScalarGeom S, ScalarRule R, ScalarSource Q, ScalarUptake U, const double* src,
-                              double* dst, const double* uv, hipStream_t s) {
-    if (!geom_ok(S) || !source_ok(Q) || !uptake_ok(U)) return hipErrorInvalidValue;
+hipError_t launch_scalar_next(ScalarGeom S, ScalarRule R, ScalarSource Q, ScalarUptake U, ScalarEnds E,
+                              const double* src, double* dst, const double* uv, hipStream_t s) {
+    if (!geom_ok(S) || !source_ok(Q) || !uptake_ok(U) || !ends_ok(E)) return hipErrorInvalidValue;
     const dim3 grid = cell_grid(S);
     if (U.a) {
-        if (Q.field) scalar_next_kernel<true, true><<<grid, 256, 0, s>>>(S, R, Q, src, dst, uv, U);
-        else scalar_next_kernel<false, true><<<grid, 256, 0, s>>>(S, R, Q, src, dst, uv, U);
+        if (Q.field) next_launch<true, true>(grid, s, S, R, Q, src, dst, uv, U, E);
+        else next_launch<false, true>(grid, s, S, R, Q, src, dst, uv, U, E);
     } else {
-        if (Q.field) scalar_next_kernel<true, false><<<grid, 256, 0, s>>>(S, R, Q, src, dst, uv, U);
-        else scalar_next_kernel<false, false><<<grid, 256, 0, s>>>(S, R, Q, src, dst, uv, U);
+        if (Q.field) next_launch<true, false>(grid, s, S, R, Q, src, dst, uv, U, E);
+        else next_launch<false, false>(grid, s, S, R, Q, src, dst, uv, U, E);
     }
     return hipGetLastError();
 }
@@ -330,11 +389,11 @@ hipError_t launch_scalar_plane_out(const double* dev, ScalarGeom S, double* out,
 }
 
 template hipError_t launch_scalar_first<double>(const double*, Layout, Halo<double>, const FieldsArgs&, ScalarGeom,
-                                                ScalarRule, ScalarSource, ScalarUptake, const double*, double*, double*,
-                                                hipStream_t);
+                                                ScalarRule, ScalarSource, ScalarUptake, ScalarEnds, const double*,
+                                                double*, double*, hipStream_t);
 template hipError_t launch_scalar_first<float>(const float*, Layout, Halo<float>, const FieldsArgs&, ScalarGeom,
-                                               ScalarRule, ScalarSource, ScalarUptake, const double*, double*, double*,
-                                               hipStream_t);
+                                               ScalarRule, ScalarSource, ScalarUptake, ScalarEnds, const double*,
+                                               double*, double*, hipStream_t);
 template hipError_t launch_scalar_init<double>(const double*, Layout, Halo<double>, const FieldsArgs&, ScalarGeom,
                                                const double*, double*, hipStream_t);
 template hipError_t launch_scalar_init<float>(const float*, Layout, Halo<float>, const FieldsArgs&, ScalarGeom,

@@ -586,6 +586,51 @@ class Lattice:
         self._check(self._lib.iblb_scalar_uptake_info(self._h, C.byref(m), C.byref(n)))
         return {"present": m.value, "substeps": n.value}
 
+    def set_scalar_ends(self, kind=("value", "outflow"), value=(0.0, 0.0), profile=(None, None)) -> None:
+        """Open ends in x for the scalar, from the next substep on (iblb_set_scalar_ends): nothing wraps from column
+        nx - 1 to column 0 any more.  kind: (left of column 0, right of column nx - 1), each "noflux", "value" or
+        "outflow" (or L.SCALAR_END_*); value: the uniform value of a "value" end; profile: [ny] each or None, the
+        value per row in its place.  Per-row accumulators of what crossed each end start at zero (`scalar_ends`).
+        Needs a scalar; replaces any previous ends.  The fluid stays periodic."""
+        def arr(a):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.size != self.ny:
+                raise ValueError(f"expected {self.ny} values, got {a.size}")
+            return a
+        kinds = [L.SCALAR_END_KINDS[k] if isinstance(k, str) else int(k) for k in kind]
+        p0, p1 = (arr(a) for a in profile)
+        ends = L.ScalarEnds((C.c_int * 2)(*kinds), (C.c_double * 2)(float(value[0]), float(value[1])),
+                            (C.c_void_p * 2)(_addr(p0), _addr(p1)))
+        self._check(self._lib.iblb_set_scalar_ends(self._h, C.byref(ends)))
+
+    def remove_scalar_ends(self) -> None:
+        """Remove the ends: the scalar is periodic in x again, its substep exactly what it is without them."""
+        self._check(self._lib.iblb_set_scalar_ends(self._h, None))
+
+    def reset_scalar_ends(self) -> None:
+        """Zero the ends' totals, last and substeps; kinds and values stay (iblb_reset_scalar_ends)."""
+        self._check(self._lib.iblb_reset_scalar_ends(self._h))
+
+    def scalar_ends(self) -> dict:
+        """{"total": (left, right), "last": (left, right), "substeps": n} (iblb_get_scalar_ends), [ny] each: the net
+        amount of C that entered every row through the end left of column 0 / right of column nx - 1 since the set or
+        the reset, and during the last substep (negative: it left)."""
+        out = [np.empty(self.ny) for _ in range(4)]
+        n = C.c_longlong(0)
+        self._check(self._lib.iblb_get_scalar_ends(self._h, *(_ptr(a) for a in out), C.byref(n)))
+        return {"total": (out[0], out[1]), "last": (out[2], out[3]), "substeps": n.value}
+
+    def scalar_ends_info(self) -> dict:
+        """{"kind", "value", "present", "substeps"} of the ends (iblb_scalar_ends_info); kind: a pair of
+        L.SCALAR_END_*, value: as given; present: L.SCALAR_ENDS_* bits, 0: none set (kind and value are then None)."""
+        k, v = (C.c_int * 2)(0, 0), (C.c_double * 2)(0.0, 0.0)
+        m, n = C.c_uint(0), C.c_longlong(0)
+        self._check(self._lib.iblb_scalar_ends_info(self._h, k, v, C.byref(m), C.byref(n)))
+        return {"kind": tuple(k) if m.value else None, "value": tuple(v) if m.value else None, "present": m.value,
+                "substeps": n.value}
+
     @property
     def steps(self) -> int:
         n = C.c_longlong(0)

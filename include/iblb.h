@@ -585,6 +585,67 @@ int iblb_get_scalar_uptake(iblb_ctx* ctx, double* total_bottom, double* total_to
 int iblb_reset_scalar_uptake(iblb_ctx* ctx);
 int iblb_scalar_uptake_info(iblb_ctx* ctx, unsigned* present, long long* substeps);
 
+/* The scalar's open ends in x.  The scalar is periodic in x because the fluid is: what leaves through column XDIM-1
+ * comes back in at column 0.  With ends set nothing wraps: each end in x has a kind, no flux, a value per row (an
+ * inlet profile) or a zero-gradient outflow, and per-row accumulators record what crossed each end, updated by every
+ * substep on the device.  It costs no readback and keeps the deep sweep; with no ends set nothing changes.  The fluid
+ * stays periodic. */
+#define IBLB_SCALAR_END_NOFLUX  0   /* halfway bounce-back: nothing crosses the end               */
+#define IBLB_SCALAR_END_VALUE   1   /* halfway anti-bounce-back: C = value at the end (an inlet)  */
+#define IBLB_SCALAR_END_OUTFLOW 2   /* zero-gradient: the missing population is the cell's own    */
+typedef struct iblb_scalar_ends {
+    int           kind[2];     /* [0]: the end left of column 0, [1]: the end right of column XDIM-1 */
+    double        value[2];    /* uniform value of a _VALUE end; required finite there               */
+    const double* profile[2];  /* [YDIM] each, only at a _VALUE end: the value of row y in place of
+                                  value[k]; NULL = the uniform one                                   */
+} iblb_scalar_ends;
+/* iblb_set_scalar_ends needs a scalar (IBLB_ERR_STATE otherwise; that covers the slabs of a group, which cannot hold
+ * one).  It copies its arrays to the device, replaces any previous ends and takes effect from the next substep that
+ * runs; it moves neither t0 nor the event count.  ends == NULL removes them: the scalar is periodic again, exactly
+ * the rule in force.  A kind outside the three, a value[k] that is not finite at a _VALUE end, profile[k] given at an
+ * end that is not _VALUE, a profile entry that is not finite: IBLB_ERR_ARG, checked before anything is touched.  The
+ * new device buffers are allocated before the old ones are freed: any error, IBLB_ERR_NOMEM included, leaves the
+ * previous ends (kinds, values, totals, substeps) as they were.  A successful set, a replacement included, starts
+ * total, last and substeps at zero.
+ * Update rule.  With ends set, one substep replaces only the x-streaming of the populations 1 and 2 at the two end
+ * columns; everything else stays as the rule in force has it (that of iblb_set_scalar, of iblb_set_scalar_source, of
+ * iblb_set_scalar_uptake): the relaxation, the walls, the uptake, and the streaming between the columns 0 .. XDIM-1.
+ * p_i is the relaxed population of the rule in force (with the source's w_i*r term when a source is set).  At x = 0:
+ * q = p_2(0, y) would leave through the left end, g_1'(0, y) has no source cell, and v = profile[0][y], or value[0]
+ * where profile[0] is NULL:
+ *   _NOFLUX:   g_1'(0, y) = q
+ *   _VALUE:    g_1'(0, y) = (2.0*w1)*v - q
+ *   _OUTFLOW:  g_1'(0, y) = p_1(0, y)           (what column 1 receives: g_1'(0, y) == g_1'(1, y))
+ *   net = g_1'(0, y) - q
+ *   total[0][y] = total[0][y] + net;   last[0][y] = net;   substeps = substeps + 1 (once per substep)
+ * At x = XDIM-1 likewise with q = p_1(XDIM-1, y), the target g_2'(XDIM-1, y), p_2(XDIM-1, y) for _OUTFLOW, and index
+ * [1].  Nothing wraps: p_1(XDIM-1, y) and p_2(0, y) reach no other column.  XDIM == 1 is valid: that one column has
+ * both ends.  Every operation in double, rounded once, no contraction; no term is skipped, so results are pinned by
+ * value (==); the sign of a zero is not part of the contract.  net is the amount of C that entered row y through that
+ * end during the substep (negative: it left).  D2Q5 has no diagonal links, so at a corner cell the wall rule and the
+ * end rule concern different directions and never meet; the streaming map stays a bijection of (cell, direction).
+ * Between walls that are not _VALUE, and with no bulk source or decay, sum(C) changes per substep by the nets of both
+ * ends plus the nets of both walls (iblb_get_scalar_uptake), up to rounding.  An event of `stride` substeps adds every
+ * one of them; each entry has one writer per substep and the substeps are ordered, so the sums are reproducible bit
+ * for bit.
+ * iblb_get_scalar_ends returns total and last of both ends, [YDIM] each, and the substeps accumulated; any pointer may
+ * be NULL, not all five (IBLB_ERR_ARG).  iblb_reset_scalar_ends zeroes total, last and substeps and keeps the kinds
+ * and values.  No ends set: IBLB_ERR_STATE from both.
+ * iblb_scalar_ends_info (any pointer may be NULL): kind and value as given, present = 1 (ends are set) | 2, 4
+ * (profile[0], profile[1]), and substeps; none set: present 0, substeps 0, kind and value untouched.
+ * iblb_set_scalar removes the ends with the scalar they belonged to, whether it replaces or removes the scalar.
+ * iblb_set_scalar_source and iblb_set_scalar_uptake keep the ends and their totals, and iblb_set_scalar_ends keeps
+ * the source and the uptake with its totals.  iblb_set_state keeps them, iblb_load_checkpoint removes them along with
+ * the scalar (checkpoints hold no ends), iblb_destroy frees them.
+ * The readers are untouched: iblb_get_scalar_wall_flux and the uptake keep their expressions, and iblb_sample_points
+ * still interpolates between column XDIM-1 and column 0, which is the fluid's periodicity and is not meaningful for C
+ * (IBLB_FIELD_C, _CUX) under open ends: sample C at 0 <= x <= XDIM-1 there. */
+int iblb_set_scalar_ends(iblb_ctx* ctx, const iblb_scalar_ends* ends);
+int iblb_get_scalar_ends(iblb_ctx* ctx, double* total_left, double* total_right, double* last_left,
+                         double* last_right, long long* substeps);
+int iblb_reset_scalar_ends(iblb_ctx* ctx);
+int iblb_scalar_ends_info(iblb_ctx* ctx, int kind[2], double value[2], unsigned* present, long long* substeps);
+
 /* Timing: when enabled (1) every collide-stream launch is bracketed by HIP events on the
  * stream it runs on; iblb_get_timing() returns the sums (and resets them if reset).  enabled = 2:
  * only the deep (K-iteration) launches are timed, by their own dispatch / completion signals (no
