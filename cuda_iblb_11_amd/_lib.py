@@ -142,6 +142,11 @@ SCALAR_ENDS_SET = 1
 SCALAR_ENDS_PROFILE = (2, 4)
 
 
+class ScalarGauges(C.Structure):
+    """struct iblb_scalar_gauges (include/iblb.h)."""
+    _fields_ = [("n_stations", C.c_int), ("station", C.c_void_p), ("n_levels", C.c_int), ("level", C.c_void_p)]
+
+
 class FieldStats(C.Structure):
     """struct iblb_field_stats (include/iblb.h)."""
     _fields_ = [
@@ -216,6 +221,11 @@ _SIGS = {
     "iblb_reset_scalar_ends": ([_vp], C.c_int),
     "iblb_scalar_ends_info": ([_vp, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_uint),
                                C.POINTER(C.c_longlong)], C.c_int),
+    "iblb_set_scalar_gauges": ([_vp, C.POINTER(ScalarGauges)], C.c_int),
+    "iblb_get_scalar_gauges": ([_vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_longlong)], C.c_int),
+    "iblb_reset_scalar_gauges": ([_vp], C.c_int),
+    "iblb_scalar_gauges_info": ([_vp, C.POINTER(C.c_int), _vp, C.POINTER(C.c_int), _vp, C.POINTER(C.c_longlong)],
+                                C.c_int),
     "iblb_set_profiling": ([_vp, C.c_int], C.c_int),
     "iblb_get_timing": ([_vp, C.POINTER(Timing), C.c_int], C.c_int),
     "iblb_get_timing_ex": ([_vp, C.POINTER(Timing), C.c_ulong, C.c_int], C.c_int),

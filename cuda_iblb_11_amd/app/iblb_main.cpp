@@ -57,6 +57,13 @@
 // per row (%.17g),
 //   y  total_left  total_right
 // the net amount of C that entered the row through each end since the run's first iteration (negative: it left).
+// IBLB_SCALAR_STATIONS=x[,x...] and IBLB_SCALAR_LEVELS=y[,y...] (either or both; they need IBLB_SCALAR) gauge that
+// scalar's transport (iblb_set_scalar_gauges): station x is the link between column x and the column to its right,
+// level y the link between row y and row y + 1, both lists strictly ascending.  At every output iteration, beside
+// <it>-scalar.dat (%.17g), <it>-stations.dat holds one line per row and <it>-levels.dat one line per column,
+//   y  right_0  left_0  right_1  left_1 ...          x  up_0  down_0  up_1  down_1 ...
+// the populations that crossed each link towards +x / -x and +y / -y, summed over the substeps since the run's first
+// iteration: right - left and up - down are the net amounts.
 #include <sys/stat.h>
 #include <sys/time.h>
 #include <unistd.h>
@@ -404,6 +411,35 @@ int main(int argc, char* argv[]) {
         sc_ends = true;
     }
 
+    // the scalar's transport gauges (extension): lists of columns and of rows
+    std::vector<int> sc_gauge[2];  // stations, levels
+    const char* const sc_gauge_env[2] = {"IBLB_SCALAR_STATIONS", "IBLB_SCALAR_LEVELS"};
+    for (int g = 0; g < 2; ++g) {
+        const char* ss = getenv(sc_gauge_env[g]);
+        if (!ss || !*ss) continue;
+        // non-negative integers separated by commas, nothing else; the range is the library's to check
+        bool ok = true;
+        for (const char* p = ss; ok;) {
+            char* end = nullptr;
+            errno = 0;
+            const long v = strtol(p, &end, 10);
+            ok = *p >= '0' && *p <= '9' && end != p && errno == 0 && v <= 0x7fffffffL && (*end == ',' || *end == 0);
+            if (!ok) break;
+            sc_gauge[g].push_back((int)v);
+            if (*end == 0) break;
+            p = end + 1;
+        }
+        if (!ok) {
+            if (lead) cerr << sc_gauge_env[g] << " must be a list of non-negative integers n[,n...], got " << ss << endl;
+            return 2;
+        }
+        if (!(sc_tau > 0.)) {
+            if (lead) cerr << sc_gauge_env[g] << " needs IBLB_SCALAR: there is no scalar to gauge" << endl;
+            return 2;
+        }
+    }
+    const bool sc_gauges = !sc_gauge[0].empty() || !sc_gauge[1].empty();
+
     const double dx = 1. / LENGTH;
     const double dt = 1. / (T);
     const double SPEED = 0.8 * 1000 / T;
@@ -504,6 +540,8 @@ int main(int argc, char* argv[]) {
     for (auto& v : up_total) v.assign(sc_uptake ? (size_t)XDIM : 0, 0.);
     std::vector<double> end_total[2];
     for (auto& v : end_total) v.assign(sc_ends ? (size_t)YDIM : 0, 0.);
+    std::vector<double> gauge_total[4];  // right, left, up, down
+    for (int g = 0; g < 4; ++g) gauge_total[g].assign(sc_gauge[g / 2].size() * (size_t)(g < 2 ? YDIM : XDIM), 0.);
     if (sc_tau > 0.) {
         std::vector<double> c0((size_t)size);
         for (int j = 0; j < size; j++) c0[j] = (unsigned int)j / XDIM < YDIM / 2 ? 1. : 0.;
@@ -526,6 +564,11 @@ int main(int argc, char* argv[]) {
                                          sc_end_kind[1] == IBLB_SCALAR_END_VALUE ? sc_end_value[1] : 0.},
                                         {nullptr, nullptr}};
             if ((rc = iblb_set_scalar_ends(ctx, &ends))) return die(ctx, rc, "iblb_set_scalar_ends");
+        }
+        if (sc_gauges) {
+            const iblb_scalar_gauges ga{(int)sc_gauge[0].size(), sc_gauge[0].empty() ? nullptr : sc_gauge[0].data(),
+                                        (int)sc_gauge[1].size(), sc_gauge[1].empty() ? nullptr : sc_gauge[1].data()};
+            if ((rc = iblb_set_scalar_gauges(ctx, &ga))) return die(ctx, rc, "iblb_set_scalar_gauges");
         }
     }
 
@@ -758,6 +801,30 @@ int main(int argc, char* argv[]) {
                 for (size_t j = 0; j < (size_t)YDIM; j++)
                     fprintf(fe, "%zu\t%.17g\t%.17g\n", j, end_total[0][j], end_total[1][j]);
                 fclose(fe);
+            }
+            if (sc_gauges) {
+                if ((rc = iblb_get_scalar_gauges(ctx, gauge_total[0].data(), gauge_total[1].data(), gauge_total[2].data(),
+                                                 gauge_total[3].data(), nullptr)))
+                    return die(ctx, rc, "iblb_get_scalar_gauges");
+                // stations: one line per row; levels: one line per column; a pair of totals per gauge
+                const char* const name[2] = {"-stations.dat", "-levels.dat"};
+                for (int g = 0; g < 2; ++g) {
+                    if (sc_gauge[g].empty()) continue;
+                    const size_t len = g == 0 ? (size_t)YDIM : (size_t)XDIM;
+                    outfile = raw_data + to_string(it) + name[g];
+                    FILE* fg = fopen(outfile.c_str(), "w");
+                    if (!fg) {
+                        fprintf(stderr, "cannot write %s: %s\n", outfile.c_str(), strerror(errno));
+                        return 1;
+                    }
+                    for (size_t j = 0; j < len; j++) {
+                        fprintf(fg, "%zu", j);
+                        for (size_t k = 0; k < sc_gauge[g].size(); k++)
+                            fprintf(fg, "\t%.17g\t%.17g", gauge_total[2 * g][k * len + j], gauge_total[2 * g + 1][k * len + j]);
+                        fprintf(fg, "\n");
+                    }
+                    fclose(fg);
+                }
             }
             if (av_stride > 0 && !av_first) {
                 outfile = raw_data + to_string(it) + "-mean.dat";

@@ -240,6 +240,12 @@ struct iblb_ctx {
     double sc_end_value[2] = {0.0, 0.0};  // as given
     unsigned sc_end_present = 0;   // the `present` bits of iblb_scalar_ends_info
     long long sc_end_substeps = 0; // substeps accumulated since the set / the reset
+    // the scalar's transport gauges (iblb_set_scalar_gauges).  sc_gau == nullptr: none.  sc_gau: one allocation, the
+    // totals right, left ([n_stations * ny] each), up, down ([n_levels * ncol] each) and then the index arrays col
+    // ([ncol]) and row ([ny]) of ScalarGauges.  Lives and dies with the scalar.
+    double* sc_gau = nullptr;
+    std::vector<int> sc_gau_station, sc_gau_level;  // as given
+    long long sc_gau_substeps = 0; // substeps accumulated since the set / the reset
     // state machine
     int phase = iblbh::PH_EMPTY;
     long long t = 0;

@@ -35,10 +35,19 @@ static void scalar_ends_free(iblb_ctx* c) {
     c->sc_end_substeps = 0;
 }
 
+static void scalar_gauges_free(iblb_ctx* c) {
+    if (c->sc_gau) (void)hipFree(c->sc_gau);
+    c->sc_gau = nullptr;
+    c->sc_gau_station.clear();
+    c->sc_gau_level.clear();
+    c->sc_gau_substeps = 0;
+}
+
 void scalar_free(iblb_ctx* c) {
     scalar_source_free(c);  // the source belongs to the scalar it was set on
     scalar_uptake_free(c);  // and so does the uptake
     scalar_ends_free(c);    // and the open ends
+    scalar_gauges_free(c);  // and the gauges
     if (c->sc_alloc) (void)hipFree(c->sc_alloc);
     c->sc_alloc = c->sc_g[0] = c->sc_g[1] = c->sc_uv = nullptr;
     c->sc_cur = 0;
@@ -71,6 +80,20 @@ static ScalarEnds scalar_ends(const iblb_ctx* c) {
     if (!c->sc_end) return ScalarEnds{{0, 0}, nullptr, nullptr, nullptr};
     const size_t n = 2 * (size_t)c->ny;
     return ScalarEnds{{c->sc_end_kind[0], c->sc_end_kind[1]}, c->sc_end, c->sc_end + n, c->sc_end + 2 * n};
+}
+
+// the doubles of the gauges' four totals: right, left ([n_stations * ny] each), up, down ([n_levels * ncol] each)
+static size_t scalar_gauges_totals(const iblb_ctx* c) {
+    return 2 * (c->sc_gau_station.size() * (size_t)c->ny + c->sc_gau_level.size() * (size_t)c->ncol);
+}
+
+// nullptr members without gauges: the launchers then run the builds without them
+static ScalarGauges scalar_gauges(const iblb_ctx* c) {
+    if (!c->sc_gau) return ScalarGauges{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const size_t ns = c->sc_gau_station.size() * (size_t)c->ny, nl = c->sc_gau_level.size() * (size_t)c->ncol;
+    double* t = c->sc_gau;
+    const int2* idx = (const int2*)(t + 2 * (ns + nl));
+    return ScalarGauges{idx, idx + c->ncol, t, t + ns, t + 2 * ns, t + 2 * ns + nl};
 }
 
 void tracers_free(iblb_ctx* c) {
@@ -135,7 +158,7 @@ static int average_update(iblb_ctx* c) {
 // evaluates it from the fluid populations and leaves it in the scratch, the others read the scratch.  With a source
 // (iblb_set_scalar_source) every substep runs the SOURCE build, without one the build that has none; likewise the
 // UPTAKE builds with an uptake (iblb_set_scalar_uptake), whose accumulators then take every substep of the event, and
-// the ENDS builds with open ends (iblb_set_scalar_ends).
+// the ENDS builds with open ends (iblb_set_scalar_ends) and the GAUGES builds with gauges (iblb_set_scalar_gauges).
 static int scalar_update(iblb_ctx* c) {
     if (!single_slab(c))  // the context joined a group after iblb_set_scalar: its lattice is the whole lattice's
         return fail(c, IBLB_ERR_UNSUPPORTED, "scalar: a lone slab only; remove it before joining a group");
@@ -147,18 +170,20 @@ static int scalar_update(iblb_ctx* c) {
     const ScalarSource Q = scalar_source(c);
     const ScalarUptake U = scalar_uptake(c);
     const ScalarEnds E = scalar_ends(c);
+    const ScalarGauges G = scalar_gauges(c);
     HIP_TRY(c, with_state(c, [&](auto* g, auto H) {
-        return launch_scalar_first(g, c->L, H, a, S, R, Q, U, E, c->sc_g[c->sc_cur], c->sc_g[c->sc_cur ^ 1], c->sc_uv,
+        return launch_scalar_first(g, c->L, H, a, S, R, Q, U, E, G, c->sc_g[c->sc_cur], c->sc_g[c->sc_cur ^ 1], c->sc_uv,
                                    c->stream);
     }));
     c->sc_cur ^= 1;
     for (int k = 1; k < c->sc_ev.stride; ++k) {
-        HIP_TRY(c, launch_scalar_next(S, R, Q, U, E, c->sc_g[c->sc_cur], c->sc_g[c->sc_cur ^ 1], c->sc_uv, c->stream));
+        HIP_TRY(c, launch_scalar_next(S, R, Q, U, E, G, c->sc_g[c->sc_cur], c->sc_g[c->sc_cur ^ 1], c->sc_uv, c->stream));
         c->sc_cur ^= 1;
     }
     c->sc_ev.advance();
     if (c->sc_up) c->sc_up_substeps += c->sc_ev.stride;
     if (c->sc_end) c->sc_end_substeps += c->sc_ev.stride;
+    if (c->sc_gau) c->sc_gau_substeps += c->sc_ev.stride;
     return IBLB_OK;
 }
 
@@ -718,6 +743,103 @@ int iblb_scalar_ends_info(iblb_ctx* c, int kind[2], double value[2], unsigned* p
     }
     if (present) *present = c->sc_end_present;
     if (substeps) *substeps = c->sc_end_substeps;
+    return IBLB_OK;
+}
+
+// ---- the scalar's transport gauges --------------------------------------------------------------------
+// n entries strictly ascending within 0 .. hi
+static bool gauge_list_ok(int n, const int* v, int hi) {
+    for (int k = 0; k < n; ++k)
+        if (v[k] < 0 || v[k] > hi || (k > 0 && v[k] <= v[k - 1])) return false;
+    return true;
+}
+
+int iblb_set_scalar_gauges(iblb_ctx* c, const iblb_scalar_gauges* ga) {
+    if (!c) return IBLB_ERR_ARG;
+    if (!c->sc_alloc)
+        return fail(c, IBLB_ERR_STATE, single_slab(c) ? "iblb_set_scalar_gauges: no scalar is set (iblb_set_scalar)"
+                                                      : "iblb_set_scalar_gauges: a slab of a group holds no scalar");
+    const int ncol = c->ncol, ny = c->ny;
+    if (ga) {
+        if (ga->n_stations < 0 || ga->n_stations > ncol) return fail(c, IBLB_ERR_ARG, "n_stations is outside 0 .. XDIM");
+        if (ga->n_levels < 0 || ga->n_levels > ny - 1) return fail(c, IBLB_ERR_ARG, "n_levels is outside 0 .. YDIM-1");
+        if (ga->n_stations == 0 && ga->n_levels == 0)
+            return fail(c, IBLB_ERR_ARG, "n_stations and n_levels are both 0 (NULL removes the gauges)");
+        if (ga->n_stations > 0 && !ga->station) return fail(c, IBLB_ERR_ARG, "station is NULL and n_stations is not 0");
+        if (ga->n_levels > 0 && !ga->level) return fail(c, IBLB_ERR_ARG, "level is NULL and n_levels is not 0");
+        if (!gauge_list_ok(ga->n_stations, ga->station, ncol - 1))
+            return fail(c, IBLB_ERR_ARG, "station must be strictly ascending within 0 .. XDIM-1");
+        if (!gauge_list_ok(ga->n_levels, ga->level, ny - 2))
+            return fail(c, IBLB_ERR_ARG, "level must be strictly ascending within 0 .. YDIM-2");
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (!ga) {
+        scalar_gauges_free(c);
+        return IBLB_OK;
+    }
+    // the index arrays of ScalarGauges: {own, the left neighbour's} per column, {own, the row below's} per row
+    std::vector<int> col(2 * (size_t)ncol, -1), row(2 * (size_t)ny, -1);
+    for (int k = 0; k < ga->n_stations; ++k) {
+        const int x = ga->station[k];
+        col[2 * (size_t)x] = k;
+        col[2 * (size_t)(x + 1 < ncol ? x + 1 : 0) + 1] = k;
+    }
+    for (int k = 0; k < ga->n_levels; ++k) {
+        const int y = ga->level[k];
+        row[2 * (size_t)y] = k;
+        row[2 * (size_t)(y + 1) + 1] = k;
+    }
+    // the new buffer first: a failed allocation leaves the previous gauges as they were
+    const size_t nt = 2 * ((size_t)ga->n_stations * ny + (size_t)ga->n_levels * ncol);
+    const size_t nb = nt * sizeof(double) + 2 * ((size_t)ncol + ny) * sizeof(int);
+    DevBuf d;
+    HIP_TRY(c, hipMalloc(&d.p, nb));
+    int* idx = (int*)((double*)d.p + nt);
+    HIP_TRY(c, hipMemsetAsync(d.p, 0, nt * sizeof(double), c->stream));
+    HIP_TRY(c, hipMemcpyAsync(idx, col.data(), col.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(idx + col.size(), row.data(), row.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    scalar_gauges_free(c);
+    c->sc_gau = (double*)d.p;
+    d.p = nullptr;
+    if (ga->n_stations > 0) c->sc_gau_station.assign(ga->station, ga->station + ga->n_stations);
+    if (ga->n_levels > 0) c->sc_gau_level.assign(ga->level, ga->level + ga->n_levels);
+    return IBLB_OK;
+}
+
+int iblb_reset_scalar_gauges(iblb_ctx* c) {
+    if (!c) return IBLB_ERR_ARG;
+    if (!c->sc_gau) return fail(c, IBLB_ERR_STATE, "iblb_reset_scalar_gauges: no gauges are set");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemsetAsync(c->sc_gau, 0, scalar_gauges_totals(c) * sizeof(double), c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->sc_gau_substeps = 0;
+    return IBLB_OK;
+}
+
+int iblb_get_scalar_gauges(iblb_ctx* c, double* right, double* left, double* up, double* down, long long* substeps) {
+    if (!c) return IBLB_ERR_ARG;
+    if (!c->sc_gau) return fail(c, IBLB_ERR_STATE, "iblb_get_scalar_gauges: no gauges are set");
+    if (!right && !left && !up && !down && !substeps) return fail(c, IBLB_ERR_ARG, "every output is NULL");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const ScalarGauges G = scalar_gauges(c);
+    const size_t ns = c->sc_gau_station.size() * (size_t)c->ny * sizeof(double);
+    const size_t nl = c->sc_gau_level.size() * (size_t)c->ncol * sizeof(double);
+    int rc = read_back(c, {{right, G.right, ns}, {left, G.left, ns}, {up, G.up, nl}, {down, G.down, nl}});
+    if (rc) return rc;
+    if (substeps) *substeps = c->sc_gau_substeps;
+    return IBLB_OK;
+}
+
+int iblb_scalar_gauges_info(iblb_ctx* c, int* n_stations, int* station, int* n_levels, int* level,
+                            long long* substeps) {
+    if (!c) return IBLB_ERR_ARG;
+    if (n_stations) *n_stations = (int)c->sc_gau_station.size();
+    if (station) std::copy(c->sc_gau_station.begin(), c->sc_gau_station.end(), station);
+    if (n_levels) *n_levels = (int)c->sc_gau_level.size();
+    if (level) std::copy(c->sc_gau_level.begin(), c->sc_gau_level.end(), level);
+    if (substeps) *substeps = c->sc_gau_substeps;
     return IBLB_OK;
 }
 

@@ -300,15 +300,29 @@ struct ScalarEnds {
     double* total;        // what crossed end k in row y since the set / the reset
     double* last;         // ... during the last substep
 };
+// The scalar's transport gauges (include/iblb.h iblb_set_scalar_gauges).  col == nullptr: none, and every launch below
+// runs the build without them.  Otherwise all six members are set.  col[x] = {the station whose column is x, the
+// station whose column is x's left neighbour (ncol - 1 for x == 0)} and row[y] = {the level whose row is y, the level
+// whose row is y - 1}, -1 where there is none: the first is the entry whose right / up the lane of cell (x, y) adds
+// to, the second the one whose left / down it adds to.  A count of 0 leaves its pair of totals empty and its indices -1.
+struct ScalarGauges {
+    const int2* col;  // [ncol]
+    const int2* row;  // [ny]
+    double* right;    // [n_stations * ny], index k * ny + y: sum of p_1(station[k], y)
+    double* left;     // ... of p_2(station[k] + 1, y)
+    double* up;       // [n_levels * ncol], index k * ncol + x: sum of p_3(x, level[k])
+    double* down;     // ... of p_4(x, level[k] + 1)
+};
 // One substep src -> dst (distinct buffers).  first: the velocity from the fluid state by cell_state of
 // field_eval.h (of FieldsArgs the window members are unused), also left in uv; next: the velocity read from uv.
 // With an uptake the lanes of rows 0 and ny - 1 also update U.total and U.last, one writer per entry; with open ends
-// the lanes of columns 0 and ncol - 1 likewise E.total and E.last.
+// the lanes of columns 0 and ncol - 1 likewise E.total and E.last; with gauges the lanes beside a gauged link G's
+// four totals.
 template <typename T>
 hipError_t launch_scalar_first(const T* f, Layout L, Halo<T> H, const FieldsArgs& a, ScalarGeom S, ScalarRule R,
-                               ScalarSource Q, ScalarUptake U, ScalarEnds E, const double* src, double* dst,
-                               double* uv, hipStream_t s);
-hipError_t launch_scalar_next(ScalarGeom S, ScalarRule R, ScalarSource Q, ScalarUptake U, ScalarEnds E,
+                               ScalarSource Q, ScalarUptake U, ScalarEnds E, ScalarGauges G, const double* src,
+                               double* dst, double* uv, hipStream_t s);
+hipError_t launch_scalar_next(ScalarGeom S, ScalarRule R, ScalarSource Q, ScalarUptake U, ScalarEnds E, ScalarGauges G,
                               const double* src, double* dst, const double* uv, hipStream_t s);
 // dst's five planes = the equilibrium of C = c[x * rows + y] at the fluid state's velocity; c may be dst's plane 0.
 template <typename T>

@@ -34,6 +34,16 @@
 // total and the substep's net amount: these accesses run along y with the lanes, contiguous like the planes'.  One
 // writer per entry per substep (with ncol == 1 one lane writes both ends' entries), no atomics.  Without ends the
 // builds without ENDS run: the kernels as they were.
+// With gauges (iblb_set_scalar_gauges) the GAUGES builds run.  A lane holds exactly the p_i that cross the four links
+// of its cell, so it adds p_1 to `right` of the station at its own column and p_2 to `left` of the station at the
+// column to its left, p_3 to `up` of the level at its own row and p_4 to `down` of the level at the row below.  Which
+// entries those are comes from two small index arrays, G.col[x] (x = blockIdx.x: one uniform 8-byte load per
+// workgroup) and G.row[y] (one 8-byte load per lane, contiguous along y, 16 bytes per row for the whole launch to
+// share); -1 means no gauge.  The station totals run along y with the lanes, contiguous like the ends'; the level
+// totals are a column stride apart like the uptake's.  A read, an add and a store per gauged lane and link, ordinary
+// vector stores, one writer per entry per substep, no atomics; no population is changed.  Under ENDS nothing crosses
+// the link right of column ncol - 1: a station there adds 0.0, which changes no value, so its lanes skip it.  Without
+// gauges the builds without GAUGES run: the kernels as they were.
 //
 // The transposes between the ABI's layouts ([y * nx + x]) and the device's go through an LDS tile so that both
 // sides coalesce.
@@ -86,10 +96,12 @@ __device__ __forceinline__ double end_cell(double q, double own, const ScalarEnd
 // their column's one wall entry (the flux or the value, by the wall's kind) from Q.walls.
 // UPTAKE: the rule of iblb_set_scalar_uptake at those two rows, with or without a source.
 // ENDS: the rule of iblb_set_scalar_ends at columns 0 and ncol - 1 for the directions 1 and 2; nothing wraps.
-template <bool SOURCE, bool UPTAKE, bool ENDS>
+// GAUGES: the totals of iblb_set_scalar_gauges; p itself goes where it went.
+template <bool SOURCE, bool UPTAKE, bool ENDS, bool GAUGES>
 __device__ __forceinline__ void scalar_push(const double g[5], double ux, double uy, const ScalarGeom& S,
                                             const ScalarRule& R, const ScalarSource& Q, const ScalarUptake& U,
-                                            const ScalarEnds& E, double sv, int x, int y, double* __restrict__ dst) {
+                                            const ScalarEnds& E, const ScalarGauges& G, double sv, int x, int y,
+                                            double* __restrict__ dst) {
 #pragma clang fp contract(off)
     const double C = (((g[0] + g[1]) + g[2]) + g[3]) + g[4];
     const double a[5] = {0.0, ux, -ux, uy, -uy};
@@ -106,6 +118,26 @@ __device__ __forceinline__ void scalar_push(const double g[5], double ux, double
         if constexpr (SOURCE) p[i] = p[i] + (i == 0 ? SW0 : SW1) * r;
     }
     const long o = (long)x * S.rows + y;
+    if constexpr (GAUGES) {
+        const int2 kc = G.col[x], kr = G.row[y];
+        // (ENDS: no link right of column ncol - 1; kc.y of column 0 names the station there)
+        if (kc.x >= 0 && !(ENDS && x + 1 >= S.ncol)) {
+            const long w = (long)kc.x * S.ny + y;
+            G.right[w] = G.right[w] + p[1];
+        }
+        if (kc.y >= 0 && !(ENDS && x == 0)) {
+            const long w = (long)kc.y * S.ny + y;
+            G.left[w] = G.left[w] + p[2];
+        }
+        if (kr.x >= 0) {
+            const long w = (long)kr.x * S.ncol + x;
+            G.up[w] = G.up[w] + p[3];
+        }
+        if (kr.y >= 0) {
+            const long w = (long)kr.y * S.ncol + x;
+            G.down[w] = G.down[w] + p[4];
+        }
+    }
     dst[o] = p[0];
     if constexpr (ENDS) {
         if (x + 1 < S.ncol) dst[S.plane + o + S.rows] = p[1];
@@ -155,13 +187,14 @@ __device__ __forceinline__ void scalar_push(const double g[5], double ux, double
 }
 
 // grid: (ncol, ceil(ny / 256)); one lane per cell.  The SOURCE builds load one more plane, Q.field; the others
-// never touch Q.  U and then E stand last: the builds without UPTAKE / ENDS never touch them, and their other
-// arguments keep their places.
-template <typename T, bool SOURCE, bool UPTAKE, bool ENDS>
+// never touch Q.  U, then E, then G stand last: the builds without UPTAKE / ENDS / GAUGES never touch them, and their
+// other arguments keep their places.
+template <typename T, bool SOURCE, bool UPTAKE, bool ENDS, bool GAUGES>
 __global__ __launch_bounds__(256) void scalar_first_kernel(const T* __restrict__ f, Layout L, Halo<T> H, FieldsArgs a,
                                                            ScalarGeom S, ScalarRule R, ScalarSource Q,
                                                            const double* __restrict__ src, double* __restrict__ dst,
-                                                           double* __restrict__ uv, ScalarUptake U, ScalarEnds E) {
+                                                           double* __restrict__ uv, ScalarUptake U, ScalarEnds E,
+                                                           ScalarGauges G) {
     const int x = blockIdx.x, y = blockIdx.y * 256 + threadIdx.x;
     if (x >= S.ncol || y >= S.ny) return;
     const long o = (long)x * S.rows + y;
@@ -172,14 +205,14 @@ __global__ __launch_bounds__(256) void scalar_first_kernel(const T* __restrict__
     cell_state<T>(f, L, H, a, x, y, pop, r, ux, uy);
     uv[o] = ux;
     uv[S.plane + o] = uy;
-    scalar_push<SOURCE, UPTAKE, ENDS>(g, ux, uy, S, R, Q, U, E, sv, x, y, dst);
+    scalar_push<SOURCE, UPTAKE, ENDS, GAUGES>(g, ux, uy, S, R, Q, U, E, G, sv, x, y, dst);
 }
 
-template <bool SOURCE, bool UPTAKE, bool ENDS>
+template <bool SOURCE, bool UPTAKE, bool ENDS, bool GAUGES>
 __global__ __launch_bounds__(256) void scalar_next_kernel(ScalarGeom S, ScalarRule R, ScalarSource Q,
                                                           const double* __restrict__ src, double* __restrict__ dst,
                                                           const double* __restrict__ uv, ScalarUptake U,
-                                                          ScalarEnds E) {
+                                                          ScalarEnds E, ScalarGauges G) {
     const int x = blockIdx.x, y = blockIdx.y * 256 + threadIdx.x;
     if (x >= S.ncol || y >= S.ny) return;
     const long o = (long)x * S.rows + y;
@@ -187,7 +220,7 @@ __global__ __launch_bounds__(256) void scalar_next_kernel(ScalarGeom S, ScalarRu
 #pragma unroll
     for (int i = 0; i < 5; ++i) g[i] = src[i * S.plane + o];
     if constexpr (SOURCE) sv = Q.field[o];
-    scalar_push<SOURCE, UPTAKE, ENDS>(g, uv[o], uv[S.plane + o], S, R, Q, U, E, sv, x, y, dst);
+    scalar_push<SOURCE, UPTAKE, ENDS, GAUGES>(g, uv[o], uv[S.plane + o], S, R, Q, U, E, G, sv, x, y, dst);
 }
 
 // The equilibrium of C = c[x * rows + y] (device layout: plane 0 of dst's own transposed input) at the cell's
@@ -291,57 +324,81 @@ inline bool ends_ok(const ScalarEnds& E) {
         if (E.kind[k] < IBLB_SCALAR_END_NOFLUX || E.kind[k] > IBLB_SCALAR_END_OUTFLOW) return false;
     return true;
 }
+// gauges have all six of their arrays or none
+inline bool gauges_ok(const ScalarGauges& G) {
+    const bool on = G.col != nullptr;
+    return (G.row != nullptr) == on && (G.right != nullptr) == on && (G.left != nullptr) == on &&
+           (G.up != nullptr) == on && (G.down != nullptr) == on;
+}
 inline dim3 cell_grid(const ScalarGeom& S) { return dim3((unsigned)S.ncol, (unsigned)((S.ny + 255) / 256)); }
 inline dim3 tile_grid(int nx, int ny, int planes) {
     return dim3((unsigned)((ny + TILE - 1) / TILE), (unsigned)((nx + TILE - 1) / TILE), (unsigned)planes);
+}
+
+// the GAUGES build or the one without, by G.col, under the SOURCE, UPTAKE and ENDS the caller chose
+template <typename T, bool SOURCE, bool UPTAKE, bool ENDS>
+void first_launch_ends(dim3 grid, hipStream_t s, const T* f, Layout L, Halo<T> H, const FieldsArgs& a, ScalarGeom S,
+                       ScalarRule R, ScalarSource Q, const double* src, double* dst, double* uv, ScalarUptake U,
+                       ScalarEnds E, ScalarGauges G) {
+    if (G.col)
+        scalar_first_kernel<T, SOURCE, UPTAKE, ENDS, true><<<grid, 256, 0, s>>>(f, L, H, a, S, R, Q, src, dst, uv, U, E, G);
+    else
+        scalar_first_kernel<T, SOURCE, UPTAKE, ENDS, false><<<grid, 256, 0, s>>>(f, L, H, a, S, R, Q, src, dst, uv, U, E, G);
+}
+
+template <bool SOURCE, bool UPTAKE, bool ENDS>
+void next_launch_ends(dim3 grid, hipStream_t s, ScalarGeom S, ScalarRule R, ScalarSource Q, const double* src,
+                      double* dst, const double* uv, ScalarUptake U, ScalarEnds E, ScalarGauges G) {
+    if (G.col) scalar_next_kernel<SOURCE, UPTAKE, ENDS, true><<<grid, 256, 0, s>>>(S, R, Q, src, dst, uv, U, E, G);
+    else scalar_next_kernel<SOURCE, UPTAKE, ENDS, false><<<grid, 256, 0, s>>>(S, R, Q, src, dst, uv, U, E, G);
 }
 
 // the ENDS build or the one without, by E.value, under the SOURCE and UPTAKE the caller chose
 template <typename T, bool SOURCE, bool UPTAKE>
 void first_launch(dim3 grid, hipStream_t s, const T* f, Layout L, Halo<T> H, const FieldsArgs& a, ScalarGeom S,
                   ScalarRule R, ScalarSource Q, const double* src, double* dst, double* uv, ScalarUptake U,
-                  ScalarEnds E) {
-    if (E.value)
-        scalar_first_kernel<T, SOURCE, UPTAKE, true><<<grid, 256, 0, s>>>(f, L, H, a, S, R, Q, src, dst, uv, U, E);
-    else scalar_first_kernel<T, SOURCE, UPTAKE, false><<<grid, 256, 0, s>>>(f, L, H, a, S, R, Q, src, dst, uv, U, E);
+                  ScalarEnds E, ScalarGauges G) {
+    if (E.value) first_launch_ends<T, SOURCE, UPTAKE, true>(grid, s, f, L, H, a, S, R, Q, src, dst, uv, U, E, G);
+    else first_launch_ends<T, SOURCE, UPTAKE, false>(grid, s, f, L, H, a, S, R, Q, src, dst, uv, U, E, G);
 }
 
 template <bool SOURCE, bool UPTAKE>
 void next_launch(dim3 grid, hipStream_t s, ScalarGeom S, ScalarRule R, ScalarSource Q, const double* src, double* dst,
-                 const double* uv, ScalarUptake U, ScalarEnds E) {
-    if (E.value) scalar_next_kernel<SOURCE, UPTAKE, true><<<grid, 256, 0, s>>>(S, R, Q, src, dst, uv, U, E);
-    else scalar_next_kernel<SOURCE, UPTAKE, false><<<grid, 256, 0, s>>>(S, R, Q, src, dst, uv, U, E);
+                 const double* uv, ScalarUptake U, ScalarEnds E, ScalarGauges G) {
+    if (E.value) next_launch_ends<SOURCE, UPTAKE, true>(grid, s, S, R, Q, src, dst, uv, U, E, G);
+    else next_launch_ends<SOURCE, UPTAKE, false>(grid, s, S, R, Q, src, dst, uv, U, E, G);
 }
 
 }  // namespace
 
 template <typename T>
 hipError_t launch_scalar_first(const T* f, Layout L, Halo<T> H, const FieldsArgs& a, ScalarGeom S, ScalarRule R,
-                               ScalarSource Q, ScalarUptake U, ScalarEnds E, const double* src, double* dst,
-                               double* uv, hipStream_t s) {
-    if (!geom_ok(S) || S.ncol != L.ncol || S.ny != L.ny || !source_ok(Q) || !uptake_ok(U) || !ends_ok(E))
+                               ScalarSource Q, ScalarUptake U, ScalarEnds E, ScalarGauges G, const double* src,
+                               double* dst, double* uv, hipStream_t s) {
+    if (!geom_ok(S) || S.ncol != L.ncol || S.ny != L.ny || !source_ok(Q) || !uptake_ok(U) || !ends_ok(E) ||
+        !gauges_ok(G))
         return hipErrorInvalidValue;
     const dim3 grid = cell_grid(S);
     if (U.a) {
-        if (Q.field) first_launch<T, true, true>(grid, s, f, L, H, a, S, R, Q, src, dst, uv, U, E);
-        else first_launch<T, false, true>(grid, s, f, L, H, a, S, R, Q, src, dst, uv, U, E);
+        if (Q.field) first_launch<T, true, true>(grid, s, f, L, H, a, S, R, Q, src, dst, uv, U, E, G);
+        else first_launch<T, false, true>(grid, s, f, L, H, a, S, R, Q, src, dst, uv, U, E, G);
     } else {
-        if (Q.field) first_launch<T, true, false>(grid, s, f, L, H, a, S, R, Q, src, dst, uv, U, E);
-        else first_launch<T, false, false>(grid, s, f, L, H, a, S, R, Q, src, dst, uv, U, E);
+        if (Q.field) first_launch<T, true, false>(grid, s, f, L, H, a, S, R, Q, src, dst, uv, U, E, G);
+        else first_launch<T, false, false>(grid, s, f, L, H, a, S, R, Q, src, dst, uv, U, E, G);
     }
     return hipGetLastError();
 }
 
-hipError_t launch_scalar_next(ScalarGeom S, ScalarRule R, ScalarSource Q, ScalarUptake U, ScalarEnds E,
+hipError_t launch_scalar_next(ScalarGeom S, ScalarRule R, ScalarSource Q, ScalarUptake U, ScalarEnds E, ScalarGauges G,
                               const double* src, double* dst, const double* uv, hipStream_t s) {
-    if (!geom_ok(S) || !source_ok(Q) || !uptake_ok(U) || !ends_ok(E)) return hipErrorInvalidValue;
+    if (!geom_ok(S) || !source_ok(Q) || !uptake_ok(U) || !ends_ok(E) || !gauges_ok(G)) return hipErrorInvalidValue;
     const dim3 grid = cell_grid(S);
     if (U.a) {
-        if (Q.field) next_launch<true, true>(grid, s, S, R, Q, src, dst, uv, U, E);
-        else next_launch<false, true>(grid, s, S, R, Q, src, dst, uv, U, E);
+        if (Q.field) next_launch<true, true>(grid, s, S, R, Q, src, dst, uv, U, E, G);
+        else next_launch<false, true>(grid, s, S, R, Q, src, dst, uv, U, E, G);
     } else {
-        if (Q.field) next_launch<true, false>(grid, s, S, R, Q, src, dst, uv, U, E);
-        else next_launch<false, false>(grid, s, S, R, Q, src, dst, uv, U, E);
+        if (Q.field) next_launch<true, false>(grid, s, S, R, Q, src, dst, uv, U, E, G);
+        else next_launch<false, false>(grid, s, S, R, Q, src, dst, uv, U, E, G);
     }
     return hipGetLastError();
 }
@@ -389,11 +446,11 @@ hipError_t launch_scalar_plane_out(const double* dev, ScalarGeom S, double* out,
 }
 
 template hipError_t launch_scalar_first<double>(const double*, Layout, Halo<double>, const FieldsArgs&, ScalarGeom,
-                                                ScalarRule, ScalarSource, ScalarUptake, ScalarEnds, const double*,
-                                                double*, double*, hipStream_t);
+                                                ScalarRule, ScalarSource, ScalarUptake, ScalarEnds, ScalarGauges,
+                                                const double*, double*, double*, hipStream_t);
 template hipError_t launch_scalar_first<float>(const float*, Layout, Halo<float>, const FieldsArgs&, ScalarGeom,
-                                               ScalarRule, ScalarSource, ScalarUptake, ScalarEnds, const double*,
-                                               double*, double*, hipStream_t);
+                                               ScalarRule, ScalarSource, ScalarUptake, ScalarEnds, ScalarGauges,
+                                               const double*, double*, double*, hipStream_t);
 template hipError_t launch_scalar_init<double>(const double*, Layout, Halo<double>, const FieldsArgs&, ScalarGeom,
                                                const double*, double*, hipStream_t);
 template hipError_t launch_scalar_init<float>(const float*, Layout, Halo<float>, const FieldsArgs&, ScalarGeom,

@@ -631,6 +631,47 @@ class Lattice:
         return {"kind": tuple(k) if m.value else None, "value": tuple(v) if m.value else None, "present": m.value,
                 "substeps": n.value}
 
+    def set_scalar_gauges(self, stations=(), levels=()) -> None:
+        """Transport gauges for the scalar, from the next substep on (iblb_set_scalar_gauges).  stations: columns x,
+        strictly ascending in 0 .. nx - 1, each the link between column x and the column to its right; levels: rows
+        y, strictly ascending in 0 .. ny - 2, each the link between row y and row y + 1.  Every substep adds the
+        populations that cross those links to per-row / per-column totals, which start at zero (`scalar_gauges`).
+        Needs a scalar; replaces any previous gauges.  No population changes."""
+        st = np.ascontiguousarray(stations, dtype=np.intc).reshape(-1)
+        lv = np.ascontiguousarray(levels, dtype=np.intc).reshape(-1)
+        ga = L.ScalarGauges(st.size, _addr(st) if st.size else None, lv.size, _addr(lv) if lv.size else None)
+        self._check(self._lib.iblb_set_scalar_gauges(self._h, C.byref(ga)))
+
+    def remove_scalar_gauges(self) -> None:
+        """Remove the gauges: the scalar's substep is then exactly what it is without them."""
+        self._check(self._lib.iblb_set_scalar_gauges(self._h, None))
+
+    def reset_scalar_gauges(self) -> None:
+        """Zero the gauges' totals and substeps; the positions stay (iblb_reset_scalar_gauges)."""
+        self._check(self._lib.iblb_reset_scalar_gauges(self._h))
+
+    def scalar_gauges(self) -> dict:
+        """{"right", "left", "up", "down", "substeps"} (iblb_get_scalar_gauges).  right, left: (n_stations, ny), the
+        sums over the substeps of p_1 of the station's column and of p_2 of the column to its right, per row; up,
+        down: (n_levels, nx), those of p_3 of the level's row and of p_4 of the row above, per column.  The net
+        amount that crossed towards +x is right - left, towards +y up - down."""
+        info = self.scalar_gauges_info()
+        ns, nl = len(info["stations"]), len(info["levels"])
+        right, left = np.empty((ns, self.ny)), np.empty((ns, self.ny))
+        up, down = np.empty((nl, self.x_count)), np.empty((nl, self.x_count))
+        n = C.c_longlong(0)
+        self._check(self._lib.iblb_get_scalar_gauges(self._h, *(_ptr(a) for a in (right, left, up, down)), C.byref(n)))
+        return {"right": right, "left": left, "up": up, "down": down, "substeps": n.value}
+
+    def scalar_gauges_info(self) -> dict:
+        """{"stations", "levels", "substeps"} of the gauges (iblb_scalar_gauges_info): the positions as given,
+        tuples; none set: both empty and substeps 0."""
+        ns, nl, n = C.c_int(0), C.c_int(0), C.c_longlong(0)
+        self._check(self._lib.iblb_scalar_gauges_info(self._h, C.byref(ns), None, C.byref(nl), None, None))
+        st, lv = np.zeros(ns.value, dtype=np.intc), np.zeros(nl.value, dtype=np.intc)
+        self._check(self._lib.iblb_scalar_gauges_info(self._h, None, _ptr(st), None, _ptr(lv), C.byref(n)))
+        return {"stations": tuple(int(v) for v in st), "levels": tuple(int(v) for v in lv), "substeps": n.value}
+
     @property
     def steps(self) -> int:
         n = C.c_longlong(0)

@@ -646,6 +646,55 @@ int iblb_get_scalar_ends(iblb_ctx* ctx, double* total_left, double* total_right,
 int iblb_reset_scalar_ends(iblb_ctx* ctx);
 int iblb_scalar_ends_info(iblb_ctx* ctx, int kind[2], double value[2], unsigned* present, long long* substeps);
 
+/* The scalar's transport gauges.  The walls and the ends record what leaves the lattice; gauges record what moves
+ * inside it: across the links between chosen columns and their right neighbours (stations) and between chosen rows and
+ * the rows above them (levels), advection and diffusion together, summed over every substep on the device.  They cost
+ * no readback and keep the deep sweep; they change no population, and with none set nothing changes. */
+typedef struct iblb_scalar_gauges {
+    int n_stations; const int* station;  /* station k: the link between column station[k] and the column to its right */
+    int n_levels;   const int* level;    /* level k: the link between row level[k] and row level[k]+1 */
+} iblb_scalar_gauges;
+/* iblb_set_scalar_gauges needs a scalar (IBLB_ERR_STATE otherwise; that covers the slabs of a group, which cannot hold
+ * one).  It copies its arrays, replaces any previous gauges and takes effect from the next substep that runs; it moves
+ * neither t0 nor the event count.  gauges == NULL removes them.  0 <= n_stations <= XDIM and 0 <= n_levels <= YDIM-1,
+ * not both 0; the entries strictly ascending with 0 <= station[k] <= XDIM-1 and 0 <= level[k] <= YDIM-2; an array is
+ * NULL only where its count is 0.  Anything else: IBLB_ERR_ARG, checked before anything is touched.  The new device
+ * buffers are allocated before the old ones are freed: any error, IBLB_ERR_NOMEM included, leaves the previous gauges
+ * (positions, totals, substeps) as they were.  A successful set, a replacement included, starts the totals and
+ * substeps at zero.
+ * Update rule.  p_i is the relaxed population of the rule in force (with the source's w_i*r term when a source is
+ * set), the p_i the ends' rule names.  With gauges set, one substep also does, for station k at column
+ * X = station[k] and every row y,
+ *   right[k][y] = right[k][y] + p_1(X, y)        (what leaves column X towards +x)
+ *   left[k][y]  = left[k][y]  + p_2(X+1, y)      (what leaves the column right of X towards -x)
+ * where, the scalar periodic, the column right of XDIM-1 is column 0 (XDIM == 1 is valid: the one column feeds both
+ * entries); with ends set (iblb_set_scalar_ends) there is no link right of column XDIM-1 and a station there adds 0.0
+ * to both entries.  For level k at row Y = level[k] and every column x,
+ *   up[k][x]   = up[k][x]   + p_3(x, Y)
+ *   down[k][x] = down[k][x] + p_4(x, Y+1)
+ * and substeps = substeps + 1, once per substep.  Every operation in double, rounded once, no contraction: results
+ * are pinned by value (==); the sign of a zero is not part of the contract.  The net amount that crossed a station
+ * towards +x is right - left, a level towards +y up - down; the subtraction is the caller's.  The gauges change no
+ * population: with gauges set the scalar, the uptake's totals and the ends' totals are bit for bit what they are
+ * without.  Each entry has one writer per substep and the substeps are ordered, so the totals are reproducible bit for
+ * bit.  The change of sum(C) over any box of columns (X0, X1] and rows (Y0, Y1] is the nets of the four gauges on its
+ * sides (walls' and ends' totals where a side is a wall or an end, the box's sum of r with a source), up to rounding.
+ * iblb_get_scalar_gauges returns right and left, [n_stations*YDIM] each, index k*YDIM + y, up and down,
+ * [n_levels*XDIM] each, index k*XDIM + x, and the substeps accumulated; any pointer may be NULL, not all five
+ * (IBLB_ERR_ARG); an array whose count is 0 is left untouched.  iblb_reset_scalar_gauges zeroes the totals and
+ * substeps and keeps the positions.  No gauges set: IBLB_ERR_STATE from both.
+ * iblb_scalar_gauges_info (any pointer may be NULL): the counts, the positions as given (station and level must hold
+ * what the counts say: ask for the counts first), and substeps; none set: counts 0, substeps 0, arrays untouched.
+ * iblb_set_scalar removes the gauges with the scalar they belonged to, whether it replaces or removes the scalar.
+ * iblb_set_state, iblb_set_scalar_source, iblb_set_scalar_uptake and iblb_set_scalar_ends keep them with their totals,
+ * and iblb_set_scalar_gauges keeps the source, the uptake and the ends with their totals.  iblb_load_checkpoint
+ * removes them along with the scalar (checkpoints hold no gauges), iblb_destroy frees them. */
+int iblb_set_scalar_gauges(iblb_ctx* ctx, const iblb_scalar_gauges* gauges);
+int iblb_get_scalar_gauges(iblb_ctx* ctx, double* right, double* left, double* up, double* down, long long* substeps);
+int iblb_reset_scalar_gauges(iblb_ctx* ctx);
+int iblb_scalar_gauges_info(iblb_ctx* ctx, int* n_stations, int* station, int* n_levels, int* level,
+                            long long* substeps);
+
 /* Timing: when enabled (1) every collide-stream launch is bracketed by HIP events on the
  * stream it runs on; iblb_get_timing() returns the sums (and resets them if reset).  enabled = 2:
  * only the deep (K-iteration) launches are timed, by their own dispatch / completion signals (no
