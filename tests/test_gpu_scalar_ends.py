@@ -6,8 +6,8 @@ The lattices, precisions, state and helpers are those of tests/test_gpu_scalar.p
 than a wave) and 16 x 300 (the end lanes span two workgroups in y), f64 and f32 storage, tau 0.8.  Every comparison of
 populations, totals and last is `==` (np.array_equal): the device does every operation of the rule once, rounded once,
 and skips no term, which is what the numpy twin does; every accumulator entry has one writer per substep and the
-substeps are ordered, so the sums carry no order of their own.  Lattices narrower than 16 columns are covered by the
-CPU tests of the restatement only.
+substeps are ordered, so the sums carry no order of their own.  Lattices narrower than 16 columns (1 x 2, 2 x 3,
+5 x 257) run in tests/test_gpu_scalar_matrix.py, with all nine pairs of end kinds under every pair of wall kinds.
 """
 import ctypes as C
 

@@ -8,7 +8,8 @@ than a wave) and 16 x 300 (two workgroups in y), f64 and f32 storage, tau 0.8.  
 reach the edges on every size: stations 0, two adjacent columns (a lane then writes `right` of its own station and
 `left` of the previous one) and nx - 1 (the wrap: column 0 writes its `left`); levels 0, two adjacent rows and ny - 2,
 and on 16 x 300 also 63 and 255, whose `up` and `down` writers sit in different waves and in different workgroups.
-Lattices narrower than 16 columns are covered by the CPU tests of the restatement only.
+Lattices narrower than 16 columns (1 x 2, 2 x 3, 5 x 257) run in tests/test_gpu_scalar_matrix.py, with every combination
+of a source, an uptake, open ends and gauges under every pair of wall kinds.
 """
 import ctypes as C
 

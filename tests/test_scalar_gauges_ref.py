@@ -4,7 +4,8 @@ down to one column; plug flow of a uniform C reads C u; the steady profile betwe
 every level; a station at the last column reads nothing under open ends; one column feeds both entries of its station;
 and the gauges never change what the rule in force returns.
 
-Narrow lattices (1, 2, 3 columns) are covered here only: the GPU suite's lattices have 16 columns or more."""
+The budgets on narrow lattices (1, 2, 3 columns) are covered here only; the device runs 1 x 2, 2 x 3 and 5 x 257
+against the twin in tests/test_gpu_scalar_matrix.py."""
 import numpy as np
 import pytest
 
