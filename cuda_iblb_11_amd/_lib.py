@@ -147,6 +147,13 @@ class ScalarGauges(C.Structure):
     _fields_ = [("n_stations", C.c_int), ("station", C.c_void_p), ("n_levels", C.c_int), ("level", C.c_void_p)]
 
 
+# the observers of iblb_save_checkpoint_ex / iblb_checkpoint_info (IBLB_CKPT_*)
+CKPT_SCALAR = 1
+CKPT_TRACERS = 2
+CKPT_AVERAGE = 4
+OBSERVERS = 7
+
+
 class FieldStats(C.Structure):
     """struct iblb_field_stats (include/iblb.h)."""
     _fields_ = [
@@ -240,6 +247,8 @@ _SIGS = {
     "iblb_gather_macro": ([_vp, C.c_int, _vp, _vp], C.c_int),
     "iblb_save_checkpoint": ([_vp, C.c_char_p], C.c_int),
     "iblb_load_checkpoint": ([_vp, C.c_char_p], C.c_int),
+    "iblb_save_checkpoint_ex": ([_vp, C.c_char_p, C.c_uint], C.c_int),
+    "iblb_checkpoint_info": ([C.c_char_p, C.POINTER(C.c_longlong), C.POINTER(C.c_uint)], C.c_int),
 }
 
 _lib = None

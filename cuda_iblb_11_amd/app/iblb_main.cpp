@@ -17,7 +17,9 @@
 //
 // Extensions (environment): IBLB_PRECISION=f32 stores populations in float; IBLB_CHECKPOINT=<prefix>
 // with IBLB_CHECKPOINT_EVERY=<iterations> writes <prefix>.rank<r> checkpoints; IBLB_RESTART=<prefix>
-// resumes from them (flux file appended, not truncated); IBLB_FIELDS_STRIDE=sx[,sy] (one GPU) also writes
+// resumes from them (flux file appended, not truncated; the checkpoints hold the observers below, iblb_save_checkpoint_ex,
+// and an observer a checkpoint does not hold, as in a file of an earlier driver, is seeded as in a fresh run);
+// IBLB_FIELDS_STRIDE=sx[,sy] (one GPU) also writes
 // <it>-fields.dat beside every <it>-fluid.dat: every sx-th column and sy-th row through iblb_get_fields,
 // x  y  u_x  u_y  vorticity (scaled like the fluid file), then the shear stress sxy in lattice units;
 // IBLB_STATS=1 (one GPU) appends one line per output iteration to <..>-stats.dat beside the flux file, from one
@@ -26,7 +28,7 @@
 // IBLB_TRACERS=nx_t,ny_t[,stride] (one GPU) seeds passive tracers (iblb_set_tracers) on a regular nx_t x ny_t grid,
 // x = (i + 0.5) XDIM / nx_t, y = (j + 0.5) (YDIM - 1) / ny_t, tracer i * ny_t + j, updated every `stride` (default 1)
 // iterations, and writes <it>-tracers.dat beside the fluid files at every output iteration (BigData or not): one line
-// x  y  laps per tracer, lattice units, %.17g.  Checkpoints hold no tracers: a restarted run seeds the grid again.
+// x  y  laps per tracer, lattice units, %.17g.  Checkpoints hold the tracers: a restarted run goes on with them.
 // IBLB_AVERAGE=stride[,nbins[,sx[,sy]]] (one GPU) lets the context average rho, u_x, u_y, their squares and u_x u_y
 // (iblb_set_average) on every sx-th column and sy-th row (default 1) of the whole lattice, one sample every `stride`
 // iterations, sample m into bin m % nbins (default 1 bin).  At every output iteration after the run's first it writes
@@ -34,12 +36,13 @@
 // bin  x  y  n  mean_rho  mean_ux  mean_uy  var_ux  var_uy  cov_uxuy   with mean = sum/n, var = sum_sq/n - mean^2,
 // cov = sum_uxuy/n - mean_ux mean_uy; a blank line after each window row; a bin with n == 0 writes nothing.  It then
 // calls iblb_reset_average: each file is the average over the preceding output interval (the first file: from the
-// run's first iteration).  Checkpoints hold no averages: a restarted run starts them again.
+// run's first iteration).  Checkpoints hold the averages: a restarted run goes on with its bins and counts.
 // IBLB_SCALAR=tau[,stride[,sx[,sy]]] (one GPU) lets the context advect and diffuse a passive scalar (iblb_set_scalar,
 // D = (tau - 0.5)/3, `stride` substeps every `stride` iterations, default 1) seeded C = 1 for y < YDIM/2 and 0 above,
 // no flux through the walls, and writes <it>-scalar.dat beside the fluid files at every output iteration (BigData or
 // not): one line  x  y  c  per sample of every sx-th column and sy-th row (default 1), lattice units, %.17g.
-// Checkpoints hold no scalar: a restarted run seeds it again.  With IBLB_STATS=1 as well, one more iblb_reduce_fields
+// Checkpoints hold the scalar with its source, uptake, ends and gauges and their totals: a restarted run goes on with
+// them (the checkpoint's configuration wins over the environment's).  With IBLB_STATS=1 as well, one more iblb_reduce_fields
 // call (IBLB_FIELD_C, _CUX, _CUY over the whole lattice) appends one line per output iteration to <..>-cstats.dat beside
 // the flux file (lattice units, %.17g):  it  sum(C)  sum(C^2)  min C  max C  sum(C u_x)  sum(C u_y)
 // IBLB_SCALAR_SOURCE=flux[,decay] (needs IBLB_SCALAR) gives that scalar a source (iblb_set_scalar_source): the amount
@@ -438,7 +441,7 @@ int main(int argc, char* argv[]) {
             return 2;
         }
     }
-    const bool sc_gauges = !sc_gauge[0].empty() || !sc_gauge[1].empty();
+    bool sc_gauges = !sc_gauge[0].empty() || !sc_gauge[1].empty();
 
     const double dx = 1. / LENGTH;
     const double dt = 1. / (T);
@@ -502,17 +505,65 @@ int main(int argc, char* argv[]) {
     const std::string restart = env_str("IBLB_RESTART", "");
     const std::string rank_sfx = ".rank" + std::to_string(rank);
     unsigned int it0 = 0;
+    // The observers a restart's checkpoint held are in place after the load, with their totals, counts and schedules:
+    // the file's configuration wins over the environment's, nothing of them is seeded or configured again, and the
+    // output files go on from the restored state.  An observer the file does not hold is seeded as in a fresh run.
+    bool tr_restored = false, av_restored = false, sc_restored = false;
+    size_t tr_n = (size_t)tr_nx * tr_ny;
+    iblb_window av_win{0, 0, ((int)XDIM - 1) / av_sx + 1, ((int)YDIM - 1) / av_sy + 1, av_sx, av_sy};
     if (!restart.empty()) {
         if ((rc = iblb_load_checkpoint(ctx, (restart + rank_sfx).c_str()))) return die(ctx, rc, "iblb_load_checkpoint");
         long long t = 0;
         iblb_get_step(ctx, &t);
         it0 = (unsigned int)t;
+        long long n = 0;
+        int stride = 0, nbins = 0;
+        if ((rc = iblb_tracer_count(ctx, &n, &stride, nullptr))) return die(ctx, rc, "iblb_tracer_count");
+        if (n > 0) {
+            tr_restored = true;
+            tr_n = (size_t)n;
+            tr_stride = stride;
+        }
+        iblb_window w{};
+        unsigned fields = 0, flags = 0;
+        if ((rc = iblb_average_info(ctx, &w, &fields, &stride, &nbins, &flags, nullptr))) return die(ctx, rc, "iblb_average_info");
+        if (fields) {
+            if (fields != (IBLB_FIELD_RHO | IBLB_FIELD_UX | IBLB_FIELD_UY) || flags != (IBLB_AVG_SQ | IBLB_AVG_UXUY) ||
+                w.x0 != 0 || w.y0 != 0) {
+                if (lead) cerr << "IBLB_RESTART: the checkpoint's average is not one this driver writes" << endl;
+                return 2;
+            }
+            av_restored = true;
+            av_win = w;
+            av_stride = stride;
+            av_nbins = nbins;
+            av_sx = w.sx;
+            av_sy = w.sy;
+        }
+        iblb_scalar sk{};
+        if ((rc = iblb_scalar_info(ctx, &sk, nullptr))) return die(ctx, rc, "iblb_scalar_info");
+        if (sk.stride > 0) {
+            sc_restored = true;
+            sc_tau = sk.tau;
+            sc_stride = sk.stride;
+            unsigned present = 0;
+            if ((rc = iblb_scalar_uptake_info(ctx, &present, nullptr))) return die(ctx, rc, "iblb_scalar_uptake_info");
+            sc_uptake = present != 0;
+            if ((rc = iblb_scalar_ends_info(ctx, nullptr, nullptr, &present, nullptr))) return die(ctx, rc, "iblb_scalar_ends_info");
+            sc_ends = present != 0;
+            int ng[2] = {0, 0};
+            if ((rc = iblb_scalar_gauges_info(ctx, &ng[0], nullptr, &ng[1], nullptr, nullptr)))
+                return die(ctx, rc, "iblb_scalar_gauges_info");
+            for (int g = 0; g < 2; ++g) sc_gauge[g].assign((size_t)ng[g], 0);
+            if ((rc = iblb_scalar_gauges_info(ctx, nullptr, sc_gauge[0].data(), nullptr, sc_gauge[1].data(), nullptr)))
+                return die(ctx, rc, "iblb_scalar_gauges_info");
+            sc_gauges = ng[0] > 0 || ng[1] > 0;
+        }
     }
-    // the tracer grid, seeded at the run's first iteration (a restarted run's too: checkpoints hold no tracers)
-    const size_t tr_n = (size_t)tr_nx * tr_ny;
+    // the tracer grid, seeded at the run's first iteration (a restarted run's too, unless its checkpoint held tracers)
     std::vector<double> tr_x(tr_n), tr_y(tr_n);
     std::vector<int> tr_laps(tr_n);
-    if (tr_n > 0) {
+    if (tr_n > 0 && !tr_restored) {
         // y fastest, like the populations: neighbouring lanes of the update kernel read neighbouring rows
         for (int i = 0; i < tr_nx; i++)
             for (int j = 0; j < tr_ny; j++) {
@@ -523,17 +574,18 @@ int main(int argc, char* argv[]) {
             return die(ctx, rc, "iblb_set_tracers");
     }
     // averaged fields: rho, u_x, u_y with their squares and u_x u_y on every av_sx-th column and av_sy-th row,
-    // from the run's first iteration (a restarted run's too: checkpoints hold no averages)
-    iblb_window av_win{0, 0, ((int)XDIM - 1) / av_sx + 1, ((int)YDIM - 1) / av_sy + 1, av_sx, av_sy};
+    // from the run's first iteration (a restarted run's too, unless its checkpoint held averages: those go on, and
+    // the run's first output iteration lies before the checkpoint)
     const size_t av_np = av_stride > 0 ? (size_t)av_win.nx * av_win.ny : 0;
     std::vector<double> av_sum(3 * av_np), av_sq(3 * av_np), av_xy(av_np);
-    bool av_first = true;  // the first output iteration writes no mean file
-    if (av_stride > 0 &&
+    bool av_first = !av_restored;  // the first output iteration writes no mean file
+    if (av_stride > 0 && !av_restored &&
         (rc = iblb_set_average(ctx, &av_win, IBLB_FIELD_RHO | IBLB_FIELD_UX | IBLB_FIELD_UY, av_stride, av_nbins,
                                IBLB_AVG_SQ | IBLB_AVG_UXUY)))
         return die(ctx, rc, "iblb_set_average");
     // the scalar: C = 1 in the lower half of the channel, 0 above, no flux through the walls, from the run's first
-    // iteration (a restarted run's too: checkpoints hold no scalar)
+    // iteration (a restarted run's too, unless its checkpoint held a scalar: that one goes on as it was, with its
+    // source, uptake, ends and gauges and their totals)
     iblb_window sc_win{0, 0, ((int)XDIM - 1) / sc_sx + 1, ((int)YDIM - 1) / sc_sy + 1, sc_sx, sc_sy};
     std::vector<double> sc_out(sc_tau > 0. ? (size_t)sc_win.nx * sc_win.ny : 0);
     std::vector<double> up_total[2];
@@ -542,7 +594,7 @@ int main(int argc, char* argv[]) {
     for (auto& v : end_total) v.assign(sc_ends ? (size_t)YDIM : 0, 0.);
     std::vector<double> gauge_total[4];  // right, left, up, down
     for (int g = 0; g < 4; ++g) gauge_total[g].assign(sc_gauge[g / 2].size() * (size_t)(g < 2 ? YDIM : XDIM), 0.);
-    if (sc_tau > 0.) {
+    if (sc_tau > 0. && !sc_restored) {
         std::vector<double> c0((size_t)size);
         for (int j = 0; j < size; j++) c0[j] = (unsigned int)j / XDIM < YDIM / 2 ? 1. : 0.;
         iblb_scalar sk{sc_tau, sc_stride, {IBLB_SCALAR_WALL_NOFLUX, IBLB_SCALAR_WALL_NOFLUX}, {0., 0.}};
@@ -877,7 +929,8 @@ int main(int argc, char* argv[]) {
         }
 
         if (ckpt_every > 0 && !ckpt.empty() && (it + 1) % ckpt_every == 0)
-            if ((rc = iblb_save_checkpoint(ctx, (ckpt + rank_sfx).c_str()))) return die(ctx, rc, "iblb_save_checkpoint");
+            if ((rc = iblb_save_checkpoint_ex(ctx, (ckpt + rank_sfx).c_str(), IBLB_CKPT_OBSERVERS)))
+                return die(ctx, rc, "iblb_save_checkpoint_ex");
         ++it;
     }
 

@@ -1,6 +1,7 @@
 // ctx.h — the context of the fused C ABI (include/iblb.h part 2) and the host helpers shared by
 // its translation units:
-//   iblb_ctx.hip   lifecycle, state, Lagrangian points, timing, checkpoint / restart
+//   iblb_ctx.hip   lifecycle, state, Lagrangian points, timing, checkpoint / restart (the files' framing:
+//                  ckpt_format.h, pure host code checked on the CPU)
 //   ctx_read.hip   the readers: the current state to the host in the reference layouts, windowed
 //                  fields and reductions, point sampling, the output gather
 //   ctx_observe.hip  what iblb_step runs between the pieces of a call: passive tracers, averaged fields,
@@ -462,6 +463,59 @@ int run_events(iblb_ctx* c);              // every observer due at c->t: the sca
 void tracers_free(iblb_ctx* c);
 void average_free(iblb_ctx* c);
 void scalar_free(iblb_ctx* c);
+
+// ---- observers in checkpoints (ctx_observe.hip; the sections' payloads are laid out above the checkpoint code
+// of iblb_ctx.hip).  kind: iblbck::K_SCALAR, K_TRACERS, K_AVERAGE (ckpt_format.h) ----
+// A section's payload parsed and checked on the host: everything its observer needs to go on
+struct CkScalar {
+    iblb_scalar cfg{};
+    long long t0 = 0, events = 0;
+    unsigned parts = 0;  // 1 source, 2 uptake, 4 ends, 8 gauges
+    std::vector<double> pops;  // iblb_get_scalar_populations
+    unsigned src_present = 0;
+    double src_decay = 0.0;
+    std::vector<double> src_field, src_walls;  // iblb_get_scalar_source; sc_src_walls
+    unsigned up_present = 0;
+    long long up_substeps = 0;
+    std::vector<double> up;  // sc_up
+    int end_kind[2] = {0, 0};
+    double end_value[2] = {0.0, 0.0};
+    unsigned end_present = 0;
+    long long end_substeps = 0;
+    std::vector<double> end;  // sc_end
+    std::vector<int> station, level;
+    long long gau_substeps = 0;
+    std::vector<double> gau;  // the four totals of sc_gau
+};
+struct CkTracers {
+    long long n = 0, t0 = 0, updates = 0;
+    int stride = 1;
+    std::vector<double> x, y;
+    std::vector<int> laps;
+};
+struct CkAverage {
+    iblb_window win{};
+    unsigned fields = 0, flags = 0;
+    int stride = 1, nbins = 1, planes = 0;
+    long long t0 = 0, samples = 0;
+    std::vector<long long> count;
+    std::vector<double> bins;  // [nbins][planes][win.ny][win.nx]: every bin as iblb_get_average returns it
+};
+struct CkObservers {
+    bool has[3] = {false, false, false};
+    CkScalar sc;
+    CkTracers tr;
+    CkAverage av;
+};
+bool observer_set(const iblb_ctx* c, int kind);
+// the payload of a set observer's section, read from the device (the streams synchronised by the caller)
+int observer_pack(iblb_ctx* c, int kind, std::vector<char>* out);
+// payload[k] of the sections has[k] of a file saved at iteration t, parsed into *o and checked against the context;
+// changes nothing in the context (but its error text); empties the payloads it has parsed
+int observers_parse(iblb_ctx* c, long long t, std::vector<char> payload[3], const bool has[3], CkObservers* o);
+// the three observers removed, then those of o set as they were saved; c->t is the file's iteration.  On a failure
+// all three are removed
+int observers_restore(iblb_ctx* c, const CkObservers& o);
 
 // ---- the read scaffold: what every reader and observer is made of ----
 // f(g, H): the populations and the halo of the current state, typed by the context's precision; the

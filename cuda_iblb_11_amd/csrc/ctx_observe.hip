@@ -2,11 +2,14 @@
 // with the state held fixed.  Passive tracers (iblb_set_tracers), time- and phase-averaged fields
 // (iblb_set_average) and the passive scalar (iblb_set_scalar), each on a Periodic schedule; iblb_step asks
 // next_event where to cut a call and run_events to run what is due there.  Built from the read scaffold of
-// ctx.h like the readers.
+// ctx.h like the readers.  At the end: the observers' sections of a checkpoint, written from and restored into the
+// context (iblb_save_checkpoint_ex, iblb_load_checkpoint in iblb_ctx.hip).
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <vector>
 
+#include "ckpt_format.h"
 #include "ctx.h"
 
 namespace iblbh {
@@ -754,6 +757,35 @@ static bool gauge_list_ok(int n, const int* v, int hi) {
     return true;
 }
 
+// sc_gau for the checked lists station and level, in *d: the four totals (zeros, or `totals` from the host) and the
+// index arrays of ScalarGauges.  Synchronises the context's stream.
+static int gauges_buffer(iblb_ctx* c, int n_stations, const int* station, int n_levels, const int* level,
+                         const double* totals, DevBuf* d) {
+    const int ncol = c->ncol, ny = c->ny;
+    // the index arrays of ScalarGauges: {own, the left neighbour's} per column, {own, the row below's} per row
+    std::vector<int> col(2 * (size_t)ncol, -1), row(2 * (size_t)ny, -1);
+    for (int k = 0; k < n_stations; ++k) {
+        const int x = station[k];
+        col[2 * (size_t)x] = k;
+        col[2 * (size_t)(x + 1 < ncol ? x + 1 : 0) + 1] = k;
+    }
+    for (int k = 0; k < n_levels; ++k) {
+        const int y = level[k];
+        row[2 * (size_t)y] = k;
+        row[2 * (size_t)(y + 1) + 1] = k;
+    }
+    const size_t nt = 2 * ((size_t)n_stations * ny + (size_t)n_levels * ncol);
+    const size_t nb = nt * sizeof(double) + 2 * ((size_t)ncol + ny) * sizeof(int);
+    HIP_TRY(c, hipMalloc(&d->p, nb));
+    int* idx = (int*)((double*)d->p + nt);
+    if (totals) HIP_TRY(c, hipMemcpyAsync(d->p, totals, nt * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    else HIP_TRY(c, hipMemsetAsync(d->p, 0, nt * sizeof(double), c->stream));
+    HIP_TRY(c, hipMemcpyAsync(idx, col.data(), col.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(idx + col.size(), row.data(), row.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return IBLB_OK;
+}
+
 int iblb_set_scalar_gauges(iblb_ctx* c, const iblb_scalar_gauges* ga) {
     if (!c) return IBLB_ERR_ARG;
     if (!c->sc_alloc)
@@ -778,28 +810,10 @@ int iblb_set_scalar_gauges(iblb_ctx* c, const iblb_scalar_gauges* ga) {
         scalar_gauges_free(c);
         return IBLB_OK;
     }
-    // the index arrays of ScalarGauges: {own, the left neighbour's} per column, {own, the row below's} per row
-    std::vector<int> col(2 * (size_t)ncol, -1), row(2 * (size_t)ny, -1);
-    for (int k = 0; k < ga->n_stations; ++k) {
-        const int x = ga->station[k];
-        col[2 * (size_t)x] = k;
-        col[2 * (size_t)(x + 1 < ncol ? x + 1 : 0) + 1] = k;
-    }
-    for (int k = 0; k < ga->n_levels; ++k) {
-        const int y = ga->level[k];
-        row[2 * (size_t)y] = k;
-        row[2 * (size_t)(y + 1) + 1] = k;
-    }
     // the new buffer first: a failed allocation leaves the previous gauges as they were
-    const size_t nt = 2 * ((size_t)ga->n_stations * ny + (size_t)ga->n_levels * ncol);
-    const size_t nb = nt * sizeof(double) + 2 * ((size_t)ncol + ny) * sizeof(int);
     DevBuf d;
-    HIP_TRY(c, hipMalloc(&d.p, nb));
-    int* idx = (int*)((double*)d.p + nt);
-    HIP_TRY(c, hipMemsetAsync(d.p, 0, nt * sizeof(double), c->stream));
-    HIP_TRY(c, hipMemcpyAsync(idx, col.data(), col.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(idx + col.size(), row.data(), row.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    int rc = gauges_buffer(c, ga->n_stations, ga->station, ga->n_levels, ga->level, nullptr, &d);
+    if (rc) return rc;
     scalar_gauges_free(c);
     c->sc_gau = (double*)d.p;
     d.p = nullptr;
@@ -844,3 +858,433 @@ int iblb_scalar_gauges_info(iblb_ctx* c, int* n_stations, int* station, int* n_l
 }
 
 }  // extern "C"
+
+// ---- observers in checkpoints ---------------------------------------------------------------------------
+// The sections' payloads (laid out above the checkpoint code of iblb_ctx.hip) written from and restored into the
+// context.  Every lattice-sized array crosses in the layout of its getter, through the getters' own transposes.
+namespace iblbh {
+namespace {
+
+// a payload under construction: 8-byte integers and doubles, arrays as raw bytes
+struct Put {
+    std::vector<char>* b;
+    void raw(const void* p, size_t n) { b->insert(b->end(), (const char*)p, (const char*)p + n); }
+    void i64(long long v) { raw(&v, 8); }
+    void f64(double v) { raw(&v, 8); }
+    // n bytes from the device (the context's stream synchronised)
+    int dev(iblb_ctx* c, const void* d, size_t n) {
+        const size_t at = b->size();
+        b->resize(at + n);
+        if (n) HIP_TRY(c, hipMemcpy(b->data() + at, d, n, hipMemcpyDeviceToHost));
+        return IBLB_OK;
+    }
+};
+
+// a payload being read: every take checks the bytes left; ok stays false after the first short take
+struct Get {
+    const char* p;
+    size_t n, pos = 0;
+    bool ok = true;
+    bool raw(void* dst, size_t bytes) {
+        if (!ok || bytes > n - pos) return ok = false;
+        if (bytes) std::memcpy(dst, p + pos, bytes);
+        pos += bytes;
+        return true;
+    }
+    long long i64() {
+        long long v = 0;
+        raw(&v, 8);
+        return v;
+    }
+    double f64() {
+        double v = 0.0;
+        raw(&v, 8);
+        return v;
+    }
+    // an int64 that must lie in [lo, hi] to be taken as an int
+    int i32(long long lo, long long hi) {
+        const long long v = i64();
+        if (v < lo || v > hi) ok = false;
+        return ok ? (int)v : 0;
+    }
+    template <typename T>
+    bool array(std::vector<T>* v, size_t count) {
+        if (!ok || count > (n - pos) / sizeof(T)) return ok = false;
+        v->resize(count);
+        return raw(v->data(), count * sizeof(T));
+    }
+    bool done() const { return ok && pos == n; }
+};
+
+// A schedule in a file: t0, the absolute iteration its runs count from — run number m (from 0) comes after iteration
+// t0 + (m + 1) stride — and the runs done.  t0 is the iteration of the set or the reset; iblb_set_state, which keeps
+// the count and starts the iterations again, moves it below zero.
+long long schedule_t0(const Periodic& ev) { return ev.next - (ev.count + 1) * ev.stride; }
+
+// the schedule (t0, stride, count) of a file saved at iteration t: the next run lies within (t, t + stride]
+bool schedule_ok(long long t, long long t0, int stride, long long count, long long* next) {
+    long long ahead = 0;
+    if (stride < 1 || count < 0 || count == LLONG_MAX) return false;
+    if (__builtin_mul_overflow(count + 1, (long long)stride, &ahead) || __builtin_add_overflow(t0, ahead, next)) return false;
+    return *next > t && *next - stride <= t;
+}
+
+int pack_scalar(iblb_ctx* c, Put w) {
+    const size_t ncol = (size_t)c->ncol, ny = (size_t)c->ny, N = ncol * ny;
+    const ScalarGeom S = scalar_geom(c);
+    const unsigned parts = (c->sc_src_present ? 1u : 0u) | (c->sc_up ? 2u : 0u) | (c->sc_end ? 4u : 0u) | (c->sc_gau ? 8u : 0u);
+    for (long long v : {(long long)c->nx, (long long)c->ny, (long long)c->sc_cfg.stride, (long long)c->sc_cfg.wall_kind[0],
+                        (long long)c->sc_cfg.wall_kind[1], schedule_t0(c->sc_ev), c->sc_ev.count, (long long)parts})
+        w.i64(v);
+    for (double v : {c->sc_cfg.tau, c->sc_cfg.wall_value[0], c->sc_cfg.wall_value[1]}) w.f64(v);
+    DevBuf d;
+    HIP_TRY(c, hipMalloc(&d.p, 5 * N * sizeof(double)));
+    HIP_TRY(c, launch_scalar_populations_out(c->sc_g[c->sc_cur], S, (double*)d.p, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    int rc = w.dev(c, d.p, 5 * N * sizeof(double));
+    if (rc) return rc;
+    if (parts & 1u) {
+        w.i64(c->sc_src_present);
+        w.f64(c->sc_src_decay);
+        HIP_TRY(c, launch_scalar_plane_out(c->sc_src_field, S, (double*)d.p, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if ((rc = w.dev(c, d.p, N * sizeof(double))) || (rc = w.dev(c, c->sc_src_walls, 4 * ncol * sizeof(double)))) return rc;
+    }
+    if (parts & 2u) {
+        w.i64(c->sc_up_present);
+        w.i64(c->sc_up_substeps);
+        if ((rc = w.dev(c, c->sc_up, 6 * ncol * sizeof(double)))) return rc;
+    }
+    if (parts & 4u) {
+        for (long long v : {(long long)c->sc_end_kind[0], (long long)c->sc_end_kind[1], (long long)c->sc_end_present,
+                            c->sc_end_substeps})
+            w.i64(v);
+        w.f64(c->sc_end_value[0]);
+        w.f64(c->sc_end_value[1]);
+        if ((rc = w.dev(c, c->sc_end, 6 * ny * sizeof(double)))) return rc;
+    }
+    if (parts & 8u) {
+        w.i64((long long)c->sc_gau_station.size());
+        w.i64((long long)c->sc_gau_level.size());
+        w.i64(c->sc_gau_substeps);
+        for (int v : c->sc_gau_station) w.i64(v);
+        for (int v : c->sc_gau_level) w.i64(v);
+        if ((rc = w.dev(c, c->sc_gau, scalar_gauges_totals(c) * sizeof(double)))) return rc;
+    }
+    return IBLB_OK;
+}
+
+int pack_tracers(iblb_ctx* c, Put w) {
+    const size_t np = (size_t)c->tr_n;
+    for (long long v : {c->tr_n, (long long)c->tr_ev.stride, schedule_t0(c->tr_ev), c->tr_ev.count}) w.i64(v);
+    int rc;
+    if ((rc = w.dev(c, c->tr_x, np * sizeof(double))) || (rc = w.dev(c, c->tr_y, np * sizeof(double))) ||
+        (rc = w.dev(c, c->tr_laps, np * sizeof(int))))
+        return rc;
+    return IBLB_OK;
+}
+
+int pack_average(iblb_ctx* c, Put w) {
+    const iblb_window& a = c->av_win;
+    for (long long v : {(long long)a.x0, (long long)a.y0, (long long)a.nx, (long long)a.ny, (long long)a.sx, (long long)a.sy,
+                        (long long)c->av_fields, (long long)c->av_flags, (long long)c->av_ev.stride, (long long)c->av_nbins,
+                        schedule_t0(c->av_ev), c->av_ev.count})
+        w.i64(v);
+    for (long long v : c->av_count) w.i64(v);
+    // every bin transposed into the ABI's layout on the device, as iblb_get_average does
+    const size_t n = average_bin_elems(c);
+    DevBuf d;
+    HIP_TRY(c, hipMalloc(&d.p, n * sizeof(double)));
+    for (int bin = 0; bin < c->av_nbins; ++bin) {
+        HIP_TRY(c, launch_average_readout(c->av_buf + (size_t)bin * n, a.nx, a.ny, c->av_planes, (double*)d.p, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        int rc = w.dev(c, d.p, n * sizeof(double));
+        if (rc) return rc;
+    }
+    return IBLB_OK;
+}
+
+int bad(iblb_ctx* c, const char* section, const char* what) {
+    return fail(c, IBLB_ERR_ARG, std::string("checkpoint, ") + section + " section: " + what);
+}
+
+int parse_scalar(iblb_ctx* c, long long t, Get r, CkScalar* s) {
+    const char* const sec = "scalar";
+    const size_t nx = (size_t)c->nx, ny = (size_t)c->ny;
+    const long long fnx = r.i64(), fny = r.i64();
+    if (!r.ok || fnx != c->nx || fny != c->ny) return bad(c, sec, "the lattice differs from the context's");
+    s->cfg.stride = r.i32(1, INT_MAX);
+    s->cfg.wall_kind[0] = r.i32(IBLB_SCALAR_WALL_NOFLUX, IBLB_SCALAR_WALL_VALUE);
+    s->cfg.wall_kind[1] = r.i32(IBLB_SCALAR_WALL_NOFLUX, IBLB_SCALAR_WALL_VALUE);
+    if (!r.ok) return bad(c, sec, "stride < 1 or an unknown wall kind");
+    s->t0 = r.i64();
+    s->events = r.i64();
+    s->parts = (unsigned)r.i32(0, 15);
+    s->cfg.tau = r.f64();
+    s->cfg.wall_value[0] = r.f64();
+    s->cfg.wall_value[1] = r.f64();
+    long long next = 0;
+    if (!r.ok || !schedule_ok(t, s->t0, s->cfg.stride, s->events, &next)) return bad(c, sec, "an inconsistent header or schedule");
+    if (!std::isfinite(s->cfg.tau) || !(s->cfg.tau > 0.5)) return bad(c, sec, "tau must be finite and > 0.5");
+    for (int k = 0; k < 2; ++k)
+        if (s->cfg.wall_kind[k] == IBLB_SCALAR_WALL_VALUE && !std::isfinite(s->cfg.wall_value[k]))
+            return bad(c, sec, "the value of a _VALUE wall is not finite");
+    if (!r.array(&s->pops, 5 * nx * ny)) return bad(c, sec, "truncated in the populations");
+    if (s->parts & 1u) {
+        s->src_present = (unsigned)r.i32(1, 63);
+        s->src_decay = r.f64();
+        if (!r.ok || !(s->src_present & 1u) || !std::isfinite(s->src_decay) || s->src_decay < 0.0)
+            return bad(c, sec, "the source's present bits or decay");
+        if (!r.array(&s->src_field, nx * ny) || !r.array(&s->src_walls, 4 * nx)) return bad(c, sec, "truncated in the source");
+    }
+    if (s->parts & 2u) {
+        s->up_present = (unsigned)r.i32(1, 7);
+        s->up_substeps = r.i64();
+        if (!r.ok || !(s->up_present & 1u) || s->up_substeps < 0) return bad(c, sec, "the uptake's present bits or substeps");
+        if (!r.array(&s->up, 6 * nx)) return bad(c, sec, "truncated in the uptake");
+    }
+    if (s->parts & 4u) {
+        s->end_kind[0] = r.i32(IBLB_SCALAR_END_NOFLUX, IBLB_SCALAR_END_OUTFLOW);
+        s->end_kind[1] = r.i32(IBLB_SCALAR_END_NOFLUX, IBLB_SCALAR_END_OUTFLOW);
+        if (!r.ok) return bad(c, sec, "an unknown end kind");
+        s->end_present = (unsigned)r.i32(1, 7);
+        s->end_substeps = r.i64();
+        s->end_value[0] = r.f64();
+        s->end_value[1] = r.f64();
+        if (!r.ok || !(s->end_present & 1u) || s->end_substeps < 0) return bad(c, sec, "the ends' present bits or substeps");
+        for (int k = 0; k < 2; ++k)
+            if (s->end_kind[k] == IBLB_SCALAR_END_VALUE && !std::isfinite(s->end_value[k]))
+                return bad(c, sec, "the value of a _VALUE end is not finite");
+        if (!r.array(&s->end, 6 * ny)) return bad(c, sec, "truncated in the ends");
+    }
+    if (s->parts & 8u) {
+        const int n_st = r.i32(0, c->nx), n_lv = r.i32(0, c->ny - 1);
+        s->gau_substeps = r.i64();
+        if (!r.ok || (n_st == 0 && n_lv == 0) || s->gau_substeps < 0)
+            return bad(c, sec, "the gauges' counts are outside 0 .. XDIM and 0 .. YDIM-1, or both 0");
+        for (int k = 0; k < n_st; ++k) s->station.push_back(r.i32(0, c->nx - 1));
+        for (int k = 0; k < n_lv; ++k) s->level.push_back(r.i32(0, c->ny - 2));
+        if (!r.ok || !gauge_list_ok(n_st, s->station.data(), c->nx - 1) || !gauge_list_ok(n_lv, s->level.data(), c->ny - 2))
+            return bad(c, sec, "the gauges' positions must be strictly ascending within the lattice");
+        if (!r.array(&s->gau, 2 * ((size_t)n_st * ny + (size_t)n_lv * nx))) return bad(c, sec, "truncated in the gauges");
+    }
+    if (!r.done()) return bad(c, sec, "its length does not match its header");
+    return IBLB_OK;
+}
+
+int parse_tracers(iblb_ctx* c, long long t, Get r, CkTracers* s) {
+    const char* const sec = "tracer";
+    s->n = r.i64();
+    s->stride = r.i32(1, INT_MAX);
+    s->t0 = r.i64();
+    s->updates = r.i64();
+    long long next = 0;
+    if (!r.ok || s->n < 1 || !schedule_ok(t, s->t0, s->stride, s->updates, &next))
+        return bad(c, sec, "n < 1, stride < 1 or an inconsistent schedule");
+    if ((unsigned long long)s->n > r.n / 20) return bad(c, sec, "truncated in the positions");
+    const size_t np = (size_t)s->n;
+    if (!r.array(&s->x, np) || !r.array(&s->y, np) || !r.array(&s->laps, np)) return bad(c, sec, "truncated in the positions");
+    if (!r.done()) return bad(c, sec, "its length does not match its header");
+    if (check_positions(c, s->n, s->x.data(), s->y.data())) return bad(c, sec, "a position outside the lattice");
+    return IBLB_OK;
+}
+
+int parse_average(iblb_ctx* c, long long t, Get r, bool scalar, CkAverage* s) {
+    const char* const sec = "average";
+    int* const w[6] = {&s->win.x0, &s->win.y0, &s->win.nx, &s->win.ny, &s->win.sx, &s->win.sy};
+    for (int* p : w) *p = r.i32(0, INT_MAX);
+    s->fields = (unsigned)r.i32(1, IBLB_FIELD_ALL | IBLB_FIELD_SCALAR);
+    s->flags = (unsigned)r.i32(0, IBLB_AVG_SQ | IBLB_AVG_UXUY);
+    s->stride = r.i32(1, INT_MAX);
+    s->nbins = r.i32(1, INT_MAX);
+    s->t0 = r.i64();
+    s->samples = r.i64();
+    long long next = 0;
+    iblb_window win;
+    int lo = 0, nxl = 0;
+    if (!r.ok || !schedule_ok(t, s->t0, s->stride, s->samples, &next)) return bad(c, sec, "an inconsistent header or schedule");
+    if (window_part(c, &s->win, &win, &lo, &nxl)) return bad(c, sec, "the window leaves the lattice");
+    if ((s->fields & ~(IBLB_FIELD_ALL | IBLB_FIELD_SCALAR)) || (s->flags & ~(unsigned)(IBLB_AVG_SQ | IBLB_AVG_UXUY)) ||
+        ((s->flags & IBLB_AVG_UXUY) && (s->fields & (IBLB_FIELD_UX | IBLB_FIELD_UY)) != (IBLB_FIELD_UX | IBLB_FIELD_UY)))
+        return bad(c, sec, "unknown field or flag bits");
+    if ((s->fields & IBLB_FIELD_SCALAR) && !scalar)
+        return bad(c, sec, "it samples the scalar and the file holds no scalar section");
+    if ((size_t)s->nbins > r.n / 8 || !r.array(&s->count, (size_t)s->nbins)) return bad(c, sec, "truncated in the counts");
+    long long total = 0;
+    for (long long v : s->count)
+        if (v < 0 || __builtin_add_overflow(total, v, &total)) return bad(c, sec, "a negative count");
+    if (total != s->samples) return bad(c, sec, "the bins' counts do not add up to the sample count");
+    s->planes = __builtin_popcount(s->fields) * ((s->flags & IBLB_AVG_SQ) ? 2 : 1) + ((s->flags & IBLB_AVG_UXUY) ? 1 : 0);
+    const size_t bin = (size_t)s->planes * (size_t)s->win.nx * (size_t)s->win.ny;  // at most 21 lattices
+    if ((size_t)s->nbins > (r.n / 8) / bin || !r.array(&s->bins, (size_t)s->nbins * bin) || !r.done())
+        return bad(c, sec, "its length does not match its header");
+    return IBLB_OK;
+}
+
+int restore_scalar(iblb_ctx* c, const CkScalar& s) {
+    const ScalarGeom S = scalar_geom(c);
+    const size_t ncol = (size_t)c->ncol, ny = (size_t)c->ny, N = ncol * ny;
+    if ((size_t)S.plane > SIZE_MAX / sizeof(double) / 12)
+        return fail(c, IBLB_ERR_NOMEM, "checkpoint: the scalar's populations exceed the address space");
+    DevBuf d, in, df, dw, du, de, dg;
+    HIP_TRY(c, hipMalloc(&d.p, 12 * (size_t)S.plane * sizeof(double)));
+    HIP_TRY(c, hipMalloc(&in.p, 5 * N * sizeof(double)));
+    double* buf = (double*)d.p;
+    HIP_TRY(c, hipMemsetAsync(buf, 0, 12 * (size_t)S.plane * sizeof(double), c->stream));
+    HIP_TRY(c, hipMemcpyAsync(in.p, s.pops.data(), 5 * N * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, launch_scalar_in((const double*)in.p, S, 5, buf, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (s.parts & 1u) {
+        HIP_TRY(c, hipMalloc(&df.p, (size_t)S.plane * sizeof(double)));
+        HIP_TRY(c, hipMalloc(&dw.p, 4 * ncol * sizeof(double)));
+        HIP_TRY(c, hipMemsetAsync(df.p, 0, (size_t)S.plane * sizeof(double), c->stream));
+        HIP_TRY(c, hipMemcpyAsync(in.p, s.src_field.data(), N * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, launch_scalar_in((const double*)in.p, S, 1, (double*)df.p, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(dw.p, s.src_walls.data(), 4 * ncol * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    if (s.parts & 2u) {
+        HIP_TRY(c, hipMalloc(&du.p, 6 * ncol * sizeof(double)));
+        HIP_TRY(c, hipMemcpy(du.p, s.up.data(), 6 * ncol * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if (s.parts & 4u) {
+        HIP_TRY(c, hipMalloc(&de.p, 6 * ny * sizeof(double)));
+        HIP_TRY(c, hipMemcpy(de.p, s.end.data(), 6 * ny * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if (s.parts & 8u) {
+        int rc = gauges_buffer(c, (int)s.station.size(), s.station.data(), (int)s.level.size(), s.level.data(), s.gau.data(), &dg);
+        if (rc) return rc;
+    }
+    // everything is on the device: the context takes it
+    auto take = [](DevBuf& b) {
+        double* p = (double*)b.p;
+        b.p = nullptr;
+        return p;
+    };
+    c->sc_alloc = take(d);
+    c->sc_g[0] = buf;
+    c->sc_g[1] = buf + 5 * S.plane;
+    c->sc_uv = buf + 10 * S.plane;
+    c->sc_cur = 0;
+    c->sc_cfg = s.cfg;
+    c->sc_ev.stride = s.cfg.stride;
+    c->sc_ev.count = s.events;
+    c->sc_ev.next = s.t0 + (s.events + 1) * s.cfg.stride;
+    if (s.parts & 1u) {
+        c->sc_src_field = take(df);
+        c->sc_src_walls = take(dw);
+        c->sc_src_decay = s.src_decay;
+        c->sc_src_present = s.src_present;
+    }
+    if (s.parts & 2u) {
+        c->sc_up = take(du);
+        c->sc_up_present = s.up_present;
+        c->sc_up_substeps = s.up_substeps;
+    }
+    if (s.parts & 4u) {
+        c->sc_end = take(de);
+        for (int k = 0; k < 2; ++k) {
+            c->sc_end_kind[k] = s.end_kind[k];
+            c->sc_end_value[k] = s.end_value[k];
+        }
+        c->sc_end_present = s.end_present;
+        c->sc_end_substeps = s.end_substeps;
+    }
+    if (s.parts & 8u) {
+        c->sc_gau = take(dg);
+        c->sc_gau_station = s.station;
+        c->sc_gau_level = s.level;
+        c->sc_gau_substeps = s.gau_substeps;
+    }
+    return IBLB_OK;
+}
+
+int restore_tracers(iblb_ctx* c, const CkTracers& s) {
+    const size_t np = (size_t)s.n;
+    DevBuf dx, dy, dl;
+    HIP_TRY(c, hipMalloc(&dx.p, np * sizeof(double)));
+    HIP_TRY(c, hipMalloc(&dy.p, np * sizeof(double)));
+    HIP_TRY(c, hipMalloc(&dl.p, np * sizeof(int)));
+    HIP_TRY(c, hipMemcpy(dx.p, s.x.data(), np * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(dy.p, s.y.data(), np * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(dl.p, s.laps.data(), np * sizeof(int), hipMemcpyHostToDevice));
+    c->tr_x = (double*)dx.p;
+    c->tr_y = (double*)dy.p;
+    c->tr_laps = (int*)dl.p;
+    dx.p = dy.p = dl.p = nullptr;
+    c->tr_n = s.n;
+    c->tr_ev.stride = s.stride;
+    c->tr_ev.count = s.updates;
+    c->tr_ev.next = s.t0 + (s.updates + 1) * s.stride;
+    return IBLB_OK;
+}
+
+int restore_average(iblb_ctx* c, const CkAverage& s) {
+    const size_t n = (size_t)s.planes * (size_t)s.win.nx * (size_t)s.win.ny, bytes = (size_t)s.nbins * n * sizeof(double);
+    DevBuf d, in;
+    HIP_TRY(c, hipMalloc(&d.p, bytes));
+    HIP_TRY(c, hipMalloc(&in.p, bytes));
+    HIP_TRY(c, hipMemcpyAsync(in.p, s.bins.data(), bytes, hipMemcpyHostToDevice, c->stream));
+    // the readout's transpose with the window's sides exchanged is its own inverse: the ABI's planes (x fastest) back
+    // into the accumulators' (y fastest)
+    for (int bin = 0; bin < s.nbins; ++bin)
+        HIP_TRY(c, launch_average_readout((const double*)in.p + (size_t)bin * n, s.win.ny, s.win.nx, s.planes,
+                                          (double*)d.p + (size_t)bin * n, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->av_buf = (double*)d.p;
+    d.p = nullptr;
+    c->av_win = s.win;
+    c->av_fields = s.fields;
+    c->av_flags = s.flags;
+    c->av_nbins = s.nbins;
+    c->av_planes = s.planes;
+    c->av_ev.stride = s.stride;
+    c->av_ev.count = s.samples;
+    c->av_ev.next = s.t0 + (s.samples + 1) * s.stride;
+    c->av_count = s.count;
+    return IBLB_OK;
+}
+
+}  // namespace
+
+bool observer_set(const iblb_ctx* c, int kind) {
+    return kind == iblbck::K_SCALAR ? c->sc_alloc != nullptr : kind == iblbck::K_TRACERS ? c->tr_n > 0 : c->av_fields != 0;
+}
+
+int observer_pack(iblb_ctx* c, int kind, std::vector<char>* out) {
+    out->clear();
+    const Put w{out};
+    return kind == iblbck::K_SCALAR ? pack_scalar(c, w) : kind == iblbck::K_TRACERS ? pack_tracers(c, w) : pack_average(c, w);
+}
+
+int observers_parse(iblb_ctx* c, long long t, std::vector<char> payload[3], const bool has[3], CkObservers* o) {
+    int rc = IBLB_OK;
+    for (int k = 0; k < 3 && !rc; ++k) {
+        o->has[k] = has[k];
+        if (!has[k]) continue;
+        const Get r{payload[k].data(), payload[k].size()};
+        rc = k == iblbck::K_SCALAR ? parse_scalar(c, t, r, &o->sc)
+             : k == iblbck::K_TRACERS ? parse_tracers(c, t, r, &o->tr)
+                                      : parse_average(c, t, r, has[iblbck::K_SCALAR], &o->av);
+        std::vector<char>().swap(payload[k]);
+    }
+    return rc;
+}
+
+int observers_restore(iblb_ctx* c, const CkObservers& o) {
+    scalar_free(c);
+    tracers_free(c);
+    average_free(c);
+    int rc = IBLB_OK;
+    if (o.has[iblbck::K_SCALAR]) rc = restore_scalar(c, o.sc);
+    if (!rc && o.has[iblbck::K_TRACERS]) rc = restore_tracers(c, o.tr);
+    if (!rc && o.has[iblbck::K_AVERAGE]) rc = restore_average(c, o.av);
+    if (rc) {
+        scalar_free(c);
+        tracers_free(c);
+        average_free(c);
+    }
+    return rc;
+}
+
+}  // namespace iblbh

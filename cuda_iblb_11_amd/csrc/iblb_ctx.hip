@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "ckpt_format.h"
 #include "ctx.h"
 
 namespace iblbh {
@@ -715,16 +716,50 @@ int iblb_synchronize(iblb_ctx* c) {
 
 // ---- checkpoint / restart -------------------------------------------------------------------------
 // File: 8-byte magic, 12 int64 fields, 6 doubles, then the stored populations g (plane i, column
-// xc, rows y; storage precision, no padding), the Lagrangian points and the cilia buffers.
+// xc, rows y; storage precision, no padding), the Lagrangian points and the cilia buffers.  That is the fluid
+// part, all that iblb_save_checkpoint writes.
+//
+// iblb_save_checkpoint_ex lets the observer part follow: one section per observer (ckpt_format.h: an 8-byte tag,
+// an int64 payload length, the payload), in the order scalar, tracers, average, closed by the end section.  A
+// payload is made of int64 (i) and double (d) fields and arrays in host byte order, without padding; nothing in
+// it depends on the device's layouts (the rows' padding, the accumulators' lane order).  XDIM = nx, YDIM = ny.
+//
+//   IBLBSCL1  i nx, ny, stride, wall_kind[0], wall_kind[1], t0, events, parts
+//             d tau, wall_value[0], wall_value[1]
+//             d[5 XDIM YDIM] the populations as iblb_get_scalar_populations returns them
+//             parts & 1, the source:  i present;  d decay;  d[XDIM YDIM] the field as iblb_get_scalar_source
+//                 returns it (zeros without one);  d[4 XDIM] wall_flux[0], wall_flux[1], wall_value[0],
+//                 wall_value[1] as held (a NULL array of the call: zeros, or the uniform wall value)
+//             parts & 2, the uptake:  i present, substeps;  d[6 XDIM] a[0], a[1], total[0], total[1], last[0],
+//                 last[1]: the derived coefficients a_k[x] as held, then what iblb_get_scalar_uptake returns
+//             parts & 4, the ends:  i kind[0], kind[1], present, substeps;  d value[0], value[1] as given;
+//                 d[6 YDIM] the rows' values (left, right) as held, then total (left, right), last (left, right)
+//             parts & 8, the gauges:  i n_stations, n_levels, substeps;  i[n_stations] station;  i[n_levels]
+//                 level;  d right, left ([n_stations YDIM] each), up, down ([n_levels XDIM] each) as
+//                 iblb_get_scalar_gauges returns them
+//   IBLBTRC1  i n, stride, t0, updates;  d[n] x;  d[n] y;  int32[n] laps
+//   IBLBAVG1  i x0, y0, nx, ny, sx, sy (the resolved window), fields, flags, stride, nbins, t0, samples
+//             i[nbins] the bins' sample counts
+//             per bin d[planes ny nx]: sum, sum_sq, sum_uxuy as iblb_get_average returns them, the planes
+//                 that `fields` and `flags` give
+//   IBLBEND1  empty
+//
+// A schedule is (t0, stride, runs done): run number m, counted from 0, comes after the absolute iteration
+// t0 + (m + 1) stride, so a restored observer goes on at the iterations it would have run at.  The scalar's
+// velocity scratch is not state (an event runs whole between the pieces of a call) and is not stored.
+//
+// Loading: the fluid header against the context, the framing (iblbck::scan), every section's payload parsed and
+// checked on the host (observers_parse) — all before anything changes.  Then the fluid part as ever, which removes
+// the three observers, then the sections' observers in the file's order (observers_restore).
 namespace {
-const char CKPT_MAGIC[8] = {'I', 'B', 'L', 'B', 'C', 'K', '0', '1'};
-enum { CK_VERSION, CK_NX, CK_NY, CK_XB, CK_NCOL, CK_PREC, CK_T, CK_NS, CK_CILIA, CK_CNUM, CK_CT, CK_CPSTEP, CK_NI };
-enum { CK_Q, CK_CSPACE, CK_TAU, CK_TAU2, CK_GX, CK_GY, CK_ND };
+using namespace iblbck;
 
 struct File {
     FILE* f = nullptr;
+    std::string unlink_path;  // removed at scope exit unless cleared: a file being written
     ~File() {
         if (f) std::fclose(f);
+        if (!unlink_path.empty()) std::remove(unlink_path.c_str());
     }
 };
 
@@ -759,26 +794,35 @@ int ck_pops(iblb_ctx* c, File& fl, bool save) {
     return IBLB_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int iblb_save_checkpoint(iblb_ctx* c, const char* path) {
-    if (!c || !path) return IBLB_ERR_ARG;
+// The fluid part and then the sections of `observers` whose observer is set, closed by the end section; without
+// such a section the fluid part alone.  Written to path.tmp and renamed; a failure leaves neither file.
+int ck_save(iblb_ctx* c, const char* path, unsigned observers) {
     if (c->phase != PH_RUN) return fail(c, IBLB_ERR_STATE, "checkpoint needs a state advanced by at least one step");
+    if ((observers & IBLB_CKPT_AVERAGE) && !(observers & IBLB_CKPT_SCALAR) && (c->av_fields & IBLB_FIELD_SCALAR))
+        return fail(c, IBLB_ERR_ARG,
+                    "IBLB_CKPT_AVERAGE without IBLB_CKPT_SCALAR: the current average samples the scalar, and such a "
+                    "file could not be restored");
     HIP_TRY(c, hipSetDevice(c->device));
     int rc = iblb_synchronize(c);
     if (rc) return rc;
+    // the payloads first: a failed read of the device leaves no file (a slab of a group holds no observer)
+    std::vector<char> payload[3];
+    bool has[3] = {false, false, false};
+    for (int k = 0; k < 3; ++k) {
+        has[k] = (observers & (1u << k)) && single_slab(c) && observer_set(c, k);
+        if (has[k] && (rc = observer_pack(c, k, &payload[k]))) return rc;
+    }
     File fl;
     const std::string tmp = std::string(path) + ".tmp";
     fl.f = std::fopen(tmp.c_str(), "wb");
     if (!fl.f) return fail(c, IBLB_ERR_ARG, std::string("cannot open ") + tmp + " for writing");
+    fl.unlink_path = tmp;
     double Q = 0.;
     HIP_TRY(c, hipMemcpy(&Q, c->d_Q, sizeof(double), hipMemcpyDeviceToHost));
     long long iv[CK_NI] = {1, c->nx, c->ny, c->x_begin, c->ncol, c->prec, c->t, c->ns, c->cilia_on ? 1 : 0,
                            c->cilia.c_num, c->cilia.T, c->cilia.p_step};
     double dv[CK_ND] = {Q, c->cilia.c_space, c->cfg.tau, c->cfg.tau2, c->coef.gx, c->coef.gy};
-    rc = ck_io(c, std::fwrite(CKPT_MAGIC, 1, 8, fl.f) == 8 && std::fwrite(iv, sizeof(iv), 1, fl.f) == 1 &&
+    rc = ck_io(c, std::fwrite(FLUID_MAGIC, 1, 8, fl.f) == 8 && std::fwrite(iv, sizeof(iv), 1, fl.f) == 1 &&
                       std::fwrite(dv, sizeof(dv), 1, fl.f) == 1);
     if (rc || (rc = ck_pops(c, fl, true))) return rc;
     const size_t ns = (size_t)c->ns;
@@ -794,10 +838,54 @@ int iblb_save_checkpoint(iblb_ctx* c, const char* path) {
             (rc = ck_dev(c, fl, true, c->cil_bpoints, 5 * (size_t)CILIA_POINTS * c->cilia.c_num * sizeof(float))))
             return rc;
     }
+    if (has[0] || has[1] || has[2]) {
+        for (int k = 0; k <= K_END; ++k) {
+            if (k < K_END && !has[k]) continue;
+            SectionHeader h;
+            std::memcpy(h.tag, TAGS[k], TAG_BYTES);
+            h.length = k < K_END ? (long long)payload[k].size() : 0;
+            if (std::fwrite(&h, sizeof(h), 1, fl.f) != 1 ||
+                (h.length && std::fwrite(payload[k].data(), 1, payload[k].size(), fl.f) != payload[k].size()))
+                return ck_io(c, false);
+        }
+    }
     const bool ok = std::fflush(fl.f) == 0;
     std::fclose(fl.f);
     fl.f = nullptr;
     if (!ok || std::rename(tmp.c_str(), path) != 0) return fail(c, IBLB_ERR_ARG, std::string("cannot write ") + path);
+    fl.unlink_path.clear();
+    return IBLB_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int iblb_save_checkpoint(iblb_ctx* c, const char* path) {
+    if (!c || !path) return IBLB_ERR_ARG;
+    return ck_save(c, path, 0);
+}
+
+int iblb_save_checkpoint_ex(iblb_ctx* c, const char* path, unsigned observers) {
+    if (!c || !path) return IBLB_ERR_ARG;
+    if (observers & ~(unsigned)IBLB_CKPT_OBSERVERS) return fail(c, IBLB_ERR_ARG, "observers: an unknown IBLB_CKPT_* bit");
+    return ck_save(c, path, observers);
+}
+
+int iblb_checkpoint_info(const char* path, long long* step, unsigned* observers) {
+    if (!path) return IBLB_ERR_ARG;
+    File fl;
+    fl.f = std::fopen(path, "rb");
+    if (!fl.f) return fail(nullptr, IBLB_ERR_ARG, std::string("cannot open ") + path);
+    long long iv[CK_NI];
+    double dv[CK_ND];
+    const long long fluid_end = read_fluid_header(fl.f, iv, dv);
+    if (fluid_end < 0) return fail(nullptr, IBLB_ERR_ARG, "not an iblb checkpoint, or a header no checkpoint has");
+    Scan sc;
+    const int st = scan(fl.f, fluid_end, &sc);
+    if (st != SCAN_OK) return fail(nullptr, IBLB_ERR_ARG, scan_message(st));
+    if (step) *step = iv[CK_T];
+    if (observers) *observers = sc.observers();
     return IBLB_OK;
 }
 
@@ -814,7 +902,7 @@ int iblb_load_checkpoint(iblb_ctx* c, const char* path) {
     char magic[8];
     long long iv[CK_NI];
     double dv[CK_ND];
-    if (std::fread(magic, 1, 8, fl.f) != 8 || std::memcmp(magic, CKPT_MAGIC, 8) != 0)
+    if (std::fread(magic, 1, 8, fl.f) != 8 || std::memcmp(magic, FLUID_MAGIC, 8) != 0)
         return fail(c, IBLB_ERR_ARG, "not an iblb checkpoint");
     if (std::fread(iv, sizeof(iv), 1, fl.f) != 1 || std::fread(dv, sizeof(dv), 1, fl.f) != 1) return ck_io(c, false);
     if (iv[CK_VERSION] != 1) return fail(c, IBLB_ERR_ARG, "unsupported checkpoint version");
@@ -824,12 +912,35 @@ int iblb_load_checkpoint(iblb_ctx* c, const char* path) {
     if (dv[CK_TAU] != c->cfg.tau || dv[CK_TAU2] != c->cfg.tau2 || dv[CK_GX] != c->coef.gx || dv[CK_GY] != c->coef.gy)
         return fail(c, IBLB_ERR_ARG, "checkpoint relaxation times / body force differ from the context");
     if (iv[CK_NS] > c->max_points) return fail(c, IBLB_ERR_ARG, "checkpoint holds more points than max_points");
+    // the observer part, if the file has one: framed, parsed and checked before anything is touched.  (A file that
+    // ends inside the fluid part fails below, while its arrays are read, as it always has.)
+    CkObservers obs;
+    Scan sc;
+    const int st = scan(fl.f, fluid_bytes(iv), &sc);
+    if (st != SCAN_OK && st != SCAN_FLUID_SHORT) return fail(c, IBLB_ERR_ARG, scan_message(st));
+    const bool observer_part = st == SCAN_OK && sc.present[K_END];
+    if (observer_part) {
+        if (!single_slab(c))
+            return fail(c, IBLB_ERR_UNSUPPORTED,
+                        "checkpoint: the file holds observers, and a slab of a group can hold none (load it into a lone "
+                        "context, or save without observers)");
+        std::vector<char> payload[3];
+        for (int k = 0; k < K_END; ++k) {
+            if (!sc.present[k]) continue;
+            payload[k].resize((size_t)sc.length[k]);
+            if (std::fseek(fl.f, (long)sc.offset[k], SEEK_SET) != 0 ||
+                (sc.length[k] && std::fread(payload[k].data(), 1, payload[k].size(), fl.f) != payload[k].size()))
+                return ck_io(c, false);
+        }
+        if ((rc = observers_parse(c, iv[CK_T], payload, sc.present, &obs))) return rc;
+    }
+    if (std::fseek(fl.f, (long)FLUID_HEADER_BYTES, SEEK_SET) != 0) return ck_io(c, false);
     // cilia configuration first (allocates its buffers), then every array
     c->ib_state = IB_NONE;
     c->phase = PH_EMPTY;
-    tracers_free(c);  // a checkpoint holds no tracers (the caller saves them with iblb_get_tracers)
-    average_free(c);  // nor averages
-    scalar_free(c);   // nor the scalar (the caller saves it with iblb_get_scalar_populations)
+    tracers_free(c);  // a checkpoint without an observer part holds no tracers,
+    average_free(c);  // no averages
+    scalar_free(c);   // and no scalar; with one, those it holds come back below
     if (iv[CK_CILIA]) {
         iblb_cilia k{(int)iv[CK_CNUM], dv[CK_CSPACE], (int)iv[CK_CT], (int)iv[CK_CPSTEP]};
         if ((rc = iblb_set_cilia(c, &k))) return rc;
@@ -875,6 +986,11 @@ int iblb_load_checkpoint(iblb_ctx* c, const char* path) {
     c->bnd_w = INT_MAX;
     c->ib_state = ib_active(c) ? IB_PENDING : IB_NONE;  // force^t is re-evaluated from g and the points
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (observer_part && (rc = observers_restore(c, obs))) {  // as any failed load: empty, without observers
+        c->phase = PH_EMPTY;
+        c->ib_state = IB_NONE;
+        return rc;
+    }
     return IBLB_OK;
 }
 

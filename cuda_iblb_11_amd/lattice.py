@@ -712,8 +712,13 @@ class Lattice:
         self._check(self._lib.iblb_synchronize(self._h))
 
     # -- checkpoint / restart -------------------------------------------------------------------
-    def save_checkpoint(self, path) -> None:
-        self._check(self._lib.iblb_save_checkpoint(self._h, os.fsencode(path)))
+    def save_checkpoint(self, path, observers: int = 0) -> None:
+        """The fluid (iblb_save_checkpoint); with observers, L.CKPT_* bits or L.OBSERVERS, also the scalar, the
+        tracers and the averages that are asked for and set (iblb_save_checkpoint_ex).  `load_checkpoint` takes both."""
+        if observers == 0:
+            self._check(self._lib.iblb_save_checkpoint(self._h, os.fsencode(path)))
+        else:
+            self._check(self._lib.iblb_save_checkpoint_ex(self._h, os.fsencode(path), int(observers)))
 
     def load_checkpoint(self, path) -> None:
         self._check(self._lib.iblb_load_checkpoint(self._h, os.fsencode(path)))
@@ -737,6 +742,15 @@ class Lattice:
         rho, u = np.empty(n), np.empty(2 * n)
         self._check(self._lib.iblb_gather_macro(self._h, int(root), _ptr(rho), _ptr(u)))
         return (rho, u) if getattr(self, "rank", 0) == int(root) else (None, None)
+
+
+def checkpoint_info(path, lib=None) -> dict:
+    """{"step", "observers"} of a checkpoint file (iblb_checkpoint_info): the iteration it was saved at and the
+    L.CKPT_* bits of the observers it holds.  Reads the file's header and framing only: no context, no device."""
+    lib = lib or L.load()
+    step, observers = C.c_longlong(0), C.c_uint(0)
+    L.check(lib.iblb_checkpoint_info(os.fsencode(path), C.byref(step), C.byref(observers)), None, lib)
+    return {"step": step.value, "observers": observers.value}
 
 
 def rccl_unique_id(lib=None) -> bytes:

@@ -374,8 +374,9 @@ int iblb_sample_points(iblb_ctx* ctx, int n, const double* x, const double* y, u
  * share those loads between neighbouring lanes and update several times faster than tracers in random order
  * (DESIGN.md section 10).
  * iblb_set_state keeps the tracers (positions, laps and the update count) and re-bases t0 to the new state's
- * step count 0: the next update follows `stride` iterations later.  Checkpoints do not hold tracers:
- * iblb_load_checkpoint removes them; the caller saves them with iblb_get_tracers and sets them again. */
+ * step count 0: the next update follows `stride` iterations later.  iblb_save_checkpoint does not hold the
+ * tracers; iblb_save_checkpoint_ex does (IBLB_CKPT_TRACERS: positions, laps, the update count and the schedule).
+ * iblb_load_checkpoint removes them and restores those its file holds. */
 int iblb_set_tracers(iblb_ctx* ctx, long long n, const double* x, const double* y, int stride);
 int iblb_get_tracers(iblb_ctx* ctx, double* x, double* y, int* laps);   /* [n] each; any may be NULL */
 /* Tracers set, their stride and the updates done since iblb_set_tracers (any may be NULL). */
@@ -422,8 +423,10 @@ int iblb_tracer_count(iblb_ctx* ctx, long long* n, int* stride, long long* updat
  * iblb_average_info returns the window (resolved: NULL became the whole lattice), fields, stride, nbins, flags
  * and the samples taken since the set or the last reset (any pointer may be NULL); fields == 0: none set.
  * iblb_set_state keeps the accumulators and counts and re-bases t0 to the new state's step count 0: the next
- * sample follows `stride` iterations later.  Checkpoints do not hold averages: iblb_load_checkpoint removes
- * averaging.  iblb_destroy frees the accumulators. */
+ * sample follows `stride` iterations later.  iblb_save_checkpoint does not hold the averages;
+ * iblb_save_checkpoint_ex does (IBLB_CKPT_AVERAGE: every bin and count and the schedule; with a scalar field only
+ * together with IBLB_CKPT_SCALAR).  iblb_load_checkpoint removes averaging and restores what its file holds.
+ * iblb_destroy frees the accumulators. */
 int iblb_set_average(iblb_ctx* ctx, const iblb_window* w, unsigned fields, int stride, int nbins, unsigned flags);
 int iblb_reset_average(iblb_ctx* ctx);
 int iblb_get_average(iblb_ctx* ctx, int bin, double* sum, double* sum_sq, double* sum_uxuy, long long* samples);
@@ -478,8 +481,9 @@ typedef struct iblb_scalar {
  * iblb_scalar_info returns the configuration and the events run since the set (either pointer may be NULL);
  * cfg->stride == 0: no scalar is set.
  * iblb_set_state keeps the scalar (populations and event count) and re-bases t0 to the new state's step count 0.
- * Checkpoints do not hold the scalar: iblb_load_checkpoint removes it; the caller saves it with
- * iblb_get_scalar_populations and restores it through g0.  A context that joins a group after the set fails its
+ * iblb_save_checkpoint does not hold the scalar; iblb_save_checkpoint_ex does (IBLB_CKPT_SCALAR: the populations,
+ * the event count and the schedule, and its source, uptake, ends and gauges).  iblb_load_checkpoint removes the scalar
+ * and restores the one its file holds.  A context that joins a group after the set fails its
  * next event with IBLB_ERR_UNSUPPORTED.  iblb_destroy frees the scalar.
  * iblb_get_scalar_wall_flux.  bottom[x], top[x], x < XDIM (either may be NULL, not both): the net amount of C that
  * entered column x through that wall during the last substep, from the stored populations:
@@ -529,7 +533,8 @@ typedef struct iblb_scalar_source {
  * _VALUE wall uses wall_value[k][x] in its expression.
  * iblb_set_scalar removes the source with the scalar it belonged to, whether it replaces or removes the scalar (a
  * replacement may change the wall kinds: set the source again).  iblb_set_state keeps the source,
- * iblb_load_checkpoint removes it along with the scalar, iblb_destroy frees it.
+ * iblb_load_checkpoint removes it along with the scalar (iblb_save_checkpoint does not hold the source;
+ * iblb_save_checkpoint_ex does, with the scalar, and the load then restores it), iblb_destroy frees it.
  * iblb_scalar_source_info (either pointer may be NULL): decay, and present = 1 (a source is set) | 2 (`source`)
  * | 4, 8 (wall_flux[0], [1]) | 16, 32 (wall_value[0], [1]); no source set: 0 and 0.0.
  * iblb_get_scalar_source returns `source` [N] in the reference layout, zeros where the source was set without it.
@@ -578,7 +583,9 @@ typedef struct iblb_scalar_uptake {
  * substeps; none set: 0 and 0.
  * iblb_set_scalar removes the uptake with the scalar it belonged to, whether it replaces or removes the scalar.
  * iblb_set_scalar_source keeps the uptake and its totals, setting or removing the source.  iblb_set_state keeps it,
- * iblb_load_checkpoint removes it along with the scalar (checkpoints hold no uptake), iblb_destroy frees it. */
+ * iblb_load_checkpoint removes it along with the scalar (iblb_save_checkpoint does not hold the uptake;
+ * iblb_save_checkpoint_ex does, with the scalar: the derived coefficients, total, last and substeps, and the load then
+ * restores them), iblb_destroy frees it. */
 int iblb_set_scalar_uptake(iblb_ctx* ctx, const iblb_scalar_uptake* up);
 int iblb_get_scalar_uptake(iblb_ctx* ctx, double* total_bottom, double* total_top, double* last_bottom,
                            double* last_top, long long* substeps);
@@ -636,7 +643,8 @@ typedef struct iblb_scalar_ends {
  * iblb_set_scalar removes the ends with the scalar they belonged to, whether it replaces or removes the scalar.
  * iblb_set_scalar_source and iblb_set_scalar_uptake keep the ends and their totals, and iblb_set_scalar_ends keeps
  * the source and the uptake with its totals.  iblb_set_state keeps them, iblb_load_checkpoint removes them along with
- * the scalar (checkpoints hold no ends), iblb_destroy frees them.
+ * the scalar (iblb_save_checkpoint does not hold the ends; iblb_save_checkpoint_ex does, with the scalar: kinds, values,
+ * total, last and substeps, and the load then restores them), iblb_destroy frees them.
  * The readers are untouched: iblb_get_scalar_wall_flux and the uptake keep their expressions, and iblb_sample_points
  * still interpolates between column XDIM-1 and column 0, which is the fluid's periodicity and is not meaningful for C
  * (IBLB_FIELD_C, _CUX) under open ends: sample C at 0 <= x <= XDIM-1 there. */
@@ -688,7 +696,8 @@ typedef struct iblb_scalar_gauges {
  * iblb_set_scalar removes the gauges with the scalar they belonged to, whether it replaces or removes the scalar.
  * iblb_set_state, iblb_set_scalar_source, iblb_set_scalar_uptake and iblb_set_scalar_ends keep them with their totals,
  * and iblb_set_scalar_gauges keeps the source, the uptake and the ends with their totals.  iblb_load_checkpoint
- * removes them along with the scalar (checkpoints hold no gauges), iblb_destroy frees them. */
+ * removes them along with the scalar (iblb_save_checkpoint does not hold the gauges; iblb_save_checkpoint_ex does, with
+ * the scalar: the positions, the four totals and substeps, and the load then restores them), iblb_destroy frees them. */
 int iblb_set_scalar_gauges(iblb_ctx* ctx, const iblb_scalar_gauges* gauges);
 int iblb_get_scalar_gauges(iblb_ctx* ctx, double* right, double* left, double* up, double* down, long long* substeps);
 int iblb_reset_scalar_gauges(iblb_ctx* ctx);
@@ -763,6 +772,48 @@ int iblb_gather_macro(iblb_ctx* ctx, int root, double* rho, double* u);
  * restore before iblb_link_local, before or after iblb_attach_rccl. */
 int iblb_save_checkpoint(iblb_ctx* ctx, const char* path);
 int iblb_load_checkpoint(iblb_ctx* ctx, const char* path);
+
+/* Checkpoints that hold the observers as well.  iblb_save_checkpoint holds the fluid alone, and loading such a
+ * file removes the tracers, the averages and the scalar.  iblb_save_checkpoint_ex writes exactly the bytes of
+ * iblb_save_checkpoint and then one section for every observer that `observers` (IBLB_CKPT_* bits) asks for and
+ * that is set, closed by an end section:
+ *   IBLB_CKPT_SCALAR   the scalar as given, its event schedule and populations, and with it its source (decay,
+ *                      field, wall arrays), its uptake (the derived coefficients, total, last, substeps), its ends
+ *                      (kinds, values, the rows' values, total, last, substeps) and its gauges (positions, the four
+ *                      totals, substeps);
+ *   IBLB_CKPT_TRACERS  n, stride, the update count, x, y and laps;
+ *   IBLB_CKPT_AVERAGE  the resolved window, fields, stride, nbins, flags, the sample counts and every plane of
+ *                      every bin.
+ * A requested observer that is not set writes no section (no error); when no section results — observers == 0,
+ * nothing set, a slab of a group, which holds no observer — the file is byte for byte iblb_save_checkpoint's, with
+ * no end section.  An unknown bit: IBLB_ERR_ARG.  IBLB_CKPT_AVERAGE without IBLB_CKPT_SCALAR while the current
+ * average holds IBLB_FIELD_C, _CUX or _CUY: IBLB_ERR_ARG (such a file could not be restored).  Before the first
+ * step: IBLB_ERR_STATE, as iblb_save_checkpoint.  On any error no file appears at path and path.tmp is removed.
+ * The file does not depend on the device's layouts; its format is described in csrc/ckpt_format.h (the framing)
+ * and above the checkpoint code of csrc/iblb_ctx.hip (the payloads).
+ *
+ * iblb_load_checkpoint takes both kinds of file.  It removes the three observers and then restores those the file
+ * holds: every *_info call and every getter then returns what it returned at the save, and stepping on gives what
+ * the uninterrupted run gives — populations, totals, last, substeps, positions, laps, bins and counts, bit for bit
+ * where the fluid restart is (no IB points).  The schedules go on by absolute iteration: a scalar of stride 3 set
+ * at iteration 0 and saved at iteration 7 has its next event after iteration 9.  The whole observer part is
+ * checked before anything is touched — the framing (known tags in order, lengths that fit the file, an end section
+ * and nothing behind it) and every section against the context (array sizes against XDIM and YDIM, positions and
+ * windows in range, wall and end kinds, stride >= 1, tau finite and > 0.5, a scalar field in the average only with
+ * a scalar section): a malformed, truncated or inconsistent observer part returns IBLB_ERR_ARG and leaves the
+ * context exactly as it was.  A file with an observer part loaded into a context attached to an RCCL group returns
+ * IBLB_ERR_UNSUPPORTED, equally before anything is touched.  A HIP or allocation failure during the restore leaves
+ * the context as any failed load does: empty (it needs a state or another load), without observers.
+ *
+ * iblb_checkpoint_info reads the fluid header and the framing of a file: the step count and the IBLB_CKPT_* bits
+ * of the sections present (either pointer may be NULL).  It needs no context and no device, and returns
+ * IBLB_ERR_ARG where iblb_load_checkpoint would refuse the file's framing. */
+#define IBLB_CKPT_SCALAR    1   /* the scalar with its source, uptake, ends and gauges, totals included */
+#define IBLB_CKPT_TRACERS   2
+#define IBLB_CKPT_AVERAGE   4
+#define IBLB_CKPT_OBSERVERS 7
+int iblb_save_checkpoint_ex(iblb_ctx* ctx, const char* path, unsigned observers);
+int iblb_checkpoint_info(const char* path, long long* step, unsigned* observers);
 
 #ifdef __cplusplus
 }
