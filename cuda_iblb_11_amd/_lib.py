@@ -93,6 +93,8 @@ QUANTITIES = {**FIELDS, "momx": 128, "momy": 256, "ke": 512, "usq": 1024, **SCAL
 # flags of iblb_set_average
 AVG_SQ = 1
 AVG_UXUY = 2
+# flag of iblb_set_history: the positions are the context's tracers
+HIST_TRACERS = 1
 # wall kinds of iblb_set_scalar
 SCALAR_WALL_NOFLUX = 0
 SCALAR_WALL_VALUE = 1
@@ -211,6 +213,13 @@ _SIGS = {
     "iblb_get_average": ([_vp, C.c_int, _vp, _vp, _vp, C.POINTER(C.c_longlong)], C.c_int),
     "iblb_average_info": ([_vp, C.POINTER(Window), C.POINTER(C.c_uint), C.POINTER(C.c_int), C.POINTER(C.c_int),
                            C.POINTER(C.c_uint), C.POINTER(C.c_longlong)], C.c_int),
+    "iblb_set_history": ([_vp, C.c_longlong, _vp, _vp, C.c_uint, C.c_int, C.c_longlong, C.c_uint], C.c_int),
+    "iblb_get_history": ([_vp, C.c_longlong, C.c_longlong, _vp, _vp], C.c_int),
+    "iblb_get_history_stats": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "iblb_get_history_points": ([_vp, _vp, _vp], C.c_int),
+    "iblb_reset_history": ([_vp], C.c_int),
+    "iblb_history_info": ([_vp, C.POINTER(C.c_longlong), C.POINTER(C.c_uint), C.POINTER(C.c_int),
+                           C.POINTER(C.c_longlong), C.POINTER(C.c_uint), C.POINTER(C.c_longlong)], C.c_int),
     "iblb_set_scalar": ([_vp, C.POINTER(Scalar), _vp, _vp], C.c_int),
     "iblb_get_scalar": ([_vp, C.POINTER(Window), _vp], C.c_int),
     "iblb_get_scalar_populations": ([_vp, _vp], C.c_int),

@@ -29,6 +29,16 @@
 // x = (i + 0.5) XDIM / nx_t, y = (j + 0.5) (YDIM - 1) / ny_t, tracer i * ny_t + j, updated every `stride` (default 1)
 // iterations, and writes <it>-tracers.dat beside the fluid files at every output iteration (BigData or not): one line
 // x  y  laps per tracer, lattice units, %.17g.  Checkpoints hold the tracers: a restarted run goes on with them.
+// IBLB_PROBES=nx_p,ny_p[,stride] (one GPU) lets the context record time series (iblb_set_history) at a regular
+// nx_p x ny_p grid of probes, x = (i + 0.5) XDIM / nx_p, y = (j + 0.5) (YDIM - 1) / ny_p, probe i * ny_p + j, one
+// record every `stride` (default 1) iterations: u_x, u_y, and C as well with IBLB_SCALAR.  The ring holds
+// INTERVAL/stride + 1 records, so none is overwritten between outputs; at every output iteration, before every
+// checkpoint and at the end of the run the driver drains the new records and appends them to <..>-probes.dat beside
+// the flux file, one line per record and probe, lattice units, %.17g:  it  p  x  y  u_x  u_y  [c]  with `it` the
+// iterations done when the record was taken.  IBLB_PATHLINES=1 (needs IBLB_TRACERS) records the tracers instead, at
+// their stride, and appends  it  p  x  y  laps  per record and tracer to <..>-paths.dat.  A context records one
+// history: setting both is refused.  No checkpoint holds a history: a restarted run sets it afresh at the restart
+// iteration and goes on appending to the same file.
 // IBLB_AVERAGE=stride[,nbins[,sx[,sy]]] (one GPU) lets the context average rho, u_x, u_y, their squares and u_x u_y
 // (iblb_set_average) on every sx-th column and sy-th row (default 1) of the whole lattice, one sample every `stride`
 // iterations, sample m into bin m % nbins (default 1 bin).  At every output iteration after the run's first it writes
@@ -248,6 +258,40 @@ int main(int argc, char* argv[]) {
         }
         if (world > 1) {  // a tracer's four cells may straddle slabs: a lone slab only (include/iblb.h)
             if (lead) cerr << "IBLB_TRACERS is not available under a launcher (WORLD_SIZE > 1): run on one GPU" << endl;
+            return 2;
+        }
+    }
+
+    // the history (extension): a regular grid of nx_p x ny_p probes, 0 = off, or the tracers' pathlines; one per context
+    int pr_nx = 0, pr_ny = 0, pr_stride = 1;
+    if (const char* ps = getenv("IBLB_PROBES"); ps && *ps) {
+        char tail = 0;
+        bool ok = sscanf(ps, "%d,%d,%d%c", &pr_nx, &pr_ny, &pr_stride, &tail) == 3;  // (a trailing character: 4)
+        if (!ok) {
+            pr_stride = 1;
+            ok = sscanf(ps, "%d,%d%c", &pr_nx, &pr_ny, &tail) == 2;
+        }
+        if (!ok || pr_nx < 1 || pr_ny < 1 || pr_stride < 1 || (long long)pr_nx * pr_ny > 100000000LL) {
+            if (lead) cerr << "IBLB_PROBES must be nx_p,ny_p[,stride] with nx_p, ny_p, stride >= 1 and at most 1e8 probes, got " << ps << endl;
+            return 2;
+        }
+        if (world > 1) {  // a probe's four cells may straddle slabs: a lone slab only (include/iblb.h)
+            if (lead) cerr << "IBLB_PROBES is not available under a launcher (WORLD_SIZE > 1): run on one GPU" << endl;
+            return 2;
+        }
+    }
+    const bool paths_on = env_int("IBLB_PATHLINES", 0) != 0;
+    if (paths_on) {
+        if (world > 1) {
+            if (lead) cerr << "IBLB_PATHLINES is not available under a launcher (WORLD_SIZE > 1): run on one GPU" << endl;
+            return 2;
+        }
+        if (tr_nx == 0) {
+            if (lead) cerr << "IBLB_PATHLINES needs IBLB_TRACERS: the pathlines are the tracers'" << endl;
+            return 2;
+        }
+        if (pr_nx > 0) {
+            if (lead) cerr << "IBLB_PROBES and IBLB_PATHLINES are both set: a context records one history (iblb_set_history)" << endl;
             return 2;
         }
     }
@@ -635,6 +679,7 @@ int main(int argc, char* argv[]) {
                              to_string_3(T_pow) + "-flux.dat";
     const std::string stats_path = flux.substr(0, flux.size() - strlen("-flux.dat")) + "-stats.dat";
     const std::string cstats_path = flux.substr(0, flux.size() - strlen("-flux.dat")) + "-cstats.dat";
+    const std::string hist_path = flux.substr(0, flux.size() - strlen("-flux.dat")) + (paths_on ? "-paths.dat" : "-probes.dat");
     const std::string parameters = raw_data + "/SimLog.txt";
 
     ofstream fsA, fsB, fsC;
@@ -651,6 +696,10 @@ int main(int argc, char* argv[]) {
             }
             if (stats_on && sc_tau > 0.) {
                 fsB.open(cstats_path.c_str(), ofstream::trunc);
+                fsB.close();
+            }
+            if (pr_nx > 0 || paths_on) {
+                fsB.open(hist_path.c_str(), ofstream::trunc);
                 fsB.close();
             }
         }
@@ -673,6 +722,61 @@ int main(int argc, char* argv[]) {
         else fsC << "Running on local GPU" << endl;
         cout << "Running Simulation...\n";
     }
+
+    // the history, set at the run's first iteration (a restarted run's too: no checkpoint holds a history, so the
+    // series goes on in the same file from the restart iteration).  The ring holds every record between two drains:
+    // the driver drains it at every output iteration, before every checkpoint and at the end of the run
+    const bool hist_on = pr_nx > 0 || paths_on;
+    const size_t hi_n = paths_on ? tr_n : (size_t)pr_nx * pr_ny;
+    const int hi_stride = paths_on ? tr_stride : pr_stride;
+    const int hi_planes = paths_on ? 3 : (sc_tau > 0. ? 3 : 2);
+    std::vector<double> pr_x(paths_on ? 0 : hi_n), pr_y(paths_on ? 0 : hi_n), hi_out;
+    std::vector<long long> hi_it;
+    long long hi_drained = 0;
+    if (hist_on) {
+        // y fastest, like the populations: neighbouring lanes of the record kernel read neighbouring rows
+        for (int i = 0; i < pr_nx; i++)
+            for (int j = 0; j < pr_ny; j++) {
+                pr_x[(size_t)i * pr_ny + j] = (i + 0.5) * XDIM / pr_nx;
+                pr_y[(size_t)i * pr_ny + j] = (j + 0.5) * (YDIM - 1) / pr_ny;
+            }
+        const unsigned hf = paths_on ? 0u : (IBLB_FIELD_UX | IBLB_FIELD_UY | (sc_tau > 0. ? IBLB_FIELD_C : 0u));
+        if ((rc = iblb_set_history(ctx, paths_on ? 0 : (long long)hi_n, pr_x.data(), pr_y.data(), hf, hi_stride,
+                                   (long long)(INTERVAL / hi_stride) + 1, paths_on ? IBLB_HIST_TRACERS : 0u)))
+            return die(ctx, rc, "iblb_set_history");
+    }
+    // the records taken since the last drain, appended to the history's file:  it  p  x  y  ux  uy  [c]  per record
+    // and probe, or  it  p  x  y  laps  per record and tracer; `it` is the record's iteration (iblb_get_step then)
+    auto drain_history = [&]() -> int {
+        long long recorded = 0;
+        if ((rc = iblb_history_info(ctx, nullptr, nullptr, nullptr, nullptr, nullptr, &recorded)))
+            return die(ctx, rc, "iblb_history_info");
+        const long long cnt = recorded - hi_drained;
+        if (cnt <= 0) return 0;
+        hi_out.resize((size_t)cnt * hi_planes * hi_n);
+        hi_it.resize((size_t)cnt);
+        if ((rc = iblb_get_history(ctx, hi_drained, cnt, hi_out.data(), hi_it.data()))) return die(ctx, rc, "iblb_get_history");
+        FILE* fh = fopen(hist_path.c_str(), "a");
+        if (!fh) {
+            fprintf(stderr, "cannot write %s: %s\n", hist_path.c_str(), strerror(errno));
+            return 1;
+        }
+        for (long long r = 0; r < cnt; r++) {
+            const double* rec = hi_out.data() + (size_t)r * hi_planes * hi_n;
+            for (size_t k = 0; k < hi_n; k++) {
+                if (paths_on) {
+                    fprintf(fh, "%lld\t%zu\t%.17g\t%.17g\t%d\n", hi_it[(size_t)r], k, rec[k], rec[hi_n + k], (int)rec[2 * hi_n + k]);
+                } else {
+                    fprintf(fh, "%lld\t%zu\t%.17g\t%.17g\t%.17g\t%.17g", hi_it[(size_t)r], k, pr_x[k], pr_y[k], rec[k], rec[hi_n + k]);
+                    if (hi_planes == 3) fprintf(fh, "\t%.17g", rec[2 * hi_n + k]);
+                    fputc('\n', fh);
+                }
+            }
+        }
+        fclose(fh);
+        hi_drained = recorded;
+        return 0;
+    };
 
     std::vector<double> rho, u, fld;
     iblb_window fwin{0, 0, 1, 1, 1, 1};
@@ -906,6 +1010,7 @@ int main(int argc, char* argv[]) {
                 if ((rc = iblb_reset_average(ctx))) return die(ctx, rc, "iblb_reset_average");
             }
             av_first = false;
+            if (hist_on && (rc = drain_history())) return rc;
             if ((rc = iblb_get_flux(ctx, &Q))) return die(ctx, rc, "iblb_get_flux");
             if (lead) {
                 fsB.open(flux.c_str(), ofstream::app);
@@ -928,11 +1033,14 @@ int main(int argc, char* argv[]) {
             fsC.close();
         }
 
-        if (ckpt_every > 0 && !ckpt.empty() && (it + 1) % ckpt_every == 0)
+        if (ckpt_every > 0 && !ckpt.empty() && (it + 1) % ckpt_every == 0) {
+            if (hist_on && (rc = drain_history())) return rc;  // no checkpoint holds the history: its file is complete up to here
             if ((rc = iblb_save_checkpoint_ex(ctx, (ckpt + rank_sfx).c_str(), IBLB_CKPT_OBSERVERS)))
                 return die(ctx, rc, "iblb_save_checkpoint_ex");
+        }
         ++it;
     }
+    if (hist_on && (rc = drain_history())) return rc;  // the records since the last output iteration
 
     if ((rc = iblb_get_flux(ctx, &Q))) return die(ctx, rc, "iblb_get_flux");
     if (lead) {

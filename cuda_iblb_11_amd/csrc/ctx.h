@@ -5,7 +5,7 @@
 //   ctx_read.hip   the readers: the current state to the host in the reference layouts, windowed
 //                  fields and reductions, point sampling, the output gather
 //   ctx_observe.hip  what iblb_step runs between the pieces of a call: passive tracers, averaged fields,
-//                  the passive scalar
+//                  the passive scalar, the history recorder
 //   ctx_step.hip   halo exchange, the one-step / two-step / deep schedules, iblb_step, local and
 //                  RCCL groups
 //   ctx_band.hip   the IB band cycle (K iterations per cycle with an owed force every iteration)
@@ -247,6 +247,17 @@ struct iblb_ctx {
     double* sc_gau = nullptr;
     std::vector<int> sc_gau_station, sc_gau_level;  // as given
     long long sc_gau_substeps = 0; // substeps accumulated since the set / the reset
+    // history recorder (iblb_set_history).  hi_n == 0: none.  With a history iblb_step stops at the iterations of
+    // hi_ev and appends record hi_ev.count to slot hi_ev.count % hi_cap of the ring there.  hi_buf: one allocation,
+    // the ring [hi_cap][hi_planes][hi_n] doubles, the statistics (eight arrays of hi_planes * hi_n 8-byte entries:
+    // count, nonfinite, sum, sum_sq, min, max, min_rec, max_rec) and, for fixed probes, the positions x [hi_n] then
+    // y [hi_n].  Under IBLB_HIST_TRACERS the positions are tr_x, tr_y, tr_laps and hi_n == tr_n
+    double* hi_buf = nullptr;
+    long long hi_n = 0, hi_cap = 0;
+    unsigned hi_fields = 0, hi_flags = 0;
+    int hi_planes = 0;
+    iblbh::Periodic hi_ev;  // count: records taken since iblb_set_history / iblb_reset_history
+    std::vector<long long> hi_iter;  // the iteration of the record in each slot
     // state machine
     int phase = iblbh::PH_EMPTY;
     long long t = 0;
@@ -459,8 +470,9 @@ int group_refused(iblb_ctx* c, const char* what);
 
 // ---- observers (ctx_observe.hip): run by iblb_step on the context's stream, no host synchronise ----
 long long next_event(const iblb_ctx* c);  // the next iteration at which an observer runs (LLONG_MAX: none set)
-int run_events(iblb_ctx* c);              // every observer due at c->t: the scalar, then the tracers and the averages
+int run_events(iblb_ctx* c);              // every observer due at c->t: the scalar, the tracers, the averages, the history
 void tracers_free(iblb_ctx* c);
+void history_free(iblb_ctx* c);
 void average_free(iblb_ctx* c);
 void scalar_free(iblb_ctx* c);
 

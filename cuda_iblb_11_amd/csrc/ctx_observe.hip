@@ -1,6 +1,7 @@
 // ctx_observe.hip — the observers of a context (ctx.h): what iblb_step runs between the pieces of a call
 // with the state held fixed.  Passive tracers (iblb_set_tracers), time- and phase-averaged fields
-// (iblb_set_average) and the passive scalar (iblb_set_scalar), each on a Periodic schedule; iblb_step asks
+// (iblb_set_average), the passive scalar (iblb_set_scalar) and the history recorder (iblb_set_history: probe
+// time series and tracer pathlines in a ring on the device), each on a Periodic schedule; iblb_step asks
 // next_event where to cut a call and run_events to run what is due there.  Built from the read scaffold of
 // ctx.h like the readers.  At the end: the observers' sections of a checkpoint, written from and restored into the
 // context (iblb_save_checkpoint_ex, iblb_load_checkpoint in iblb_ctx.hip).
@@ -119,6 +120,37 @@ void average_free(iblb_ctx* c) {
     c->av_count.clear();
 }
 
+void history_free(iblb_ctx* c) {
+    if (c->hi_buf) (void)hipFree(c->hi_buf);
+    c->hi_buf = nullptr;
+    c->hi_n = c->hi_cap = 0;
+    c->hi_fields = c->hi_flags = 0;
+    c->hi_planes = 0;
+    c->hi_ev.clear();
+    c->hi_iter.clear();
+}
+
+// the parts of hi_buf (ctx.h): entries of one plane set, doubles of one record, and the parts' places
+static size_t history_entries(const iblb_ctx* c) { return (size_t)c->hi_planes * (size_t)c->hi_n; }
+static double* history_stats_base(const iblb_ctx* c) { return c->hi_buf + (size_t)c->hi_cap * history_entries(c); }
+static HistoryStats history_stats(const iblb_ctx* c) {
+    const size_t e = history_entries(c);
+    double* b = history_stats_base(c);
+    return HistoryStats{(long long*)b,   (long long*)(b + e),     b + 2 * e, b + 3 * e, b + 4 * e,
+                        b + 5 * e,       (long long*)(b + 6 * e), (long long*)(b + 7 * e)};
+}
+static const double* history_xy(const iblb_ctx* c) { return history_stats_base(c) + 8 * history_entries(c); }
+
+// the statistics with nothing seen, for e entries: zeros, min = +inf, max = -inf, the record numbers -1
+static std::vector<double> history_stats_blank(size_t e) {
+    std::vector<double> h(8 * e, 0.0);
+    std::fill_n(h.begin() + 4 * e, e, HUGE_VAL);
+    std::fill_n(h.begin() + 5 * e, e, -HUGE_VAL);
+    const long long none = -1;
+    for (size_t j = 6 * e; j < 8 * e; ++j) std::memcpy(&h[j], &none, sizeof none);
+    return h;
+}
+
 static size_t average_bin_elems(const iblb_ctx* c) {
     return (size_t)c->av_planes * (size_t)c->av_win.nx * (size_t)c->av_win.ny;
 }
@@ -190,21 +222,53 @@ static int scalar_update(iblb_ctx* c) {
     return IBLB_OK;
 }
 
+// One record of the history from the current state, on the context's stream: the state prepared as for a
+// reader (the band streams joined, the owed IB force evaluated), then one launch that writes the record into
+// its slot of the ring and folds it into the statistics.  The slot's iteration is kept on the host.
+static int history_update(iblb_ctx* c) {
+    if (!single_slab(c))  // the context joined a group after iblb_set_history: its probes are the whole lattice's
+        return fail(c, IBLB_ERR_UNSUPPORTED, "history: a lone slab only; remove it before joining a group");
+    int rc = check_scalar_fields(c, c->hi_fields);  // (iblb_set_scalar keeps the scalar under such a history)
+    if (rc) return rc;
+    const bool follow = (c->hi_flags & IBLB_HIST_TRACERS) != 0;
+    if (follow && c->tr_n != c->hi_n)  // (iblb_set_tracers keeps the tracers under such a history)
+        return fail(c, IBLB_ERR_STATE, "history: the tracers it follows are gone");
+    rc = band_join(c);
+    if (rc || (rc = prepare_read(c))) return rc;
+    const long long m = c->hi_ev.count;
+    const size_t slot = (size_t)(m % c->hi_cap);
+    const FieldsArgs a = point_args(c, c->hi_fields);
+    const double* x = follow ? c->tr_x : history_xy(c);
+    const double* y = follow ? c->tr_y : history_xy(c) + c->hi_n;
+    const int* laps = follow ? c->tr_laps : nullptr;
+    double* rec = c->hi_buf + slot * history_entries(c);
+    const HistoryStats st = history_stats(c);
+    HIP_TRY(c, with_state(c, [&](auto* g, auto H) {
+        return launch_history_record(g, c->L, H, a, (long)c->hi_n, x, y, laps, m, rec, st, c->stream);
+    }));
+    c->hi_iter[slot] = c->t;
+    c->hi_ev.advance();
+    return IBLB_OK;
+}
+
 long long next_event(const iblb_ctx* c) {
     long long next = LLONG_MAX;
     if (c->tr_n > 0) next = std::min(next, c->tr_ev.next);
     if (c->av_fields) next = std::min(next, c->av_ev.next);
     if (c->sc_alloc) next = std::min(next, c->sc_ev.next);
+    if (c->hi_n > 0) next = std::min(next, c->hi_ev.next);
     return next;
 }
 
 // No observer changes the fluid state, but an average may sample the scalar: the scalar's event runs first, so
-// that a sample at a common iteration sees C after that iteration's event (include/iblb.h)
+// that a sample at a common iteration sees C after that iteration's event (include/iblb.h).  The history runs
+// last: a pathline record holds the tracers after that iteration's update
 int run_events(iblb_ctx* c) {
     int rc = IBLB_OK;
     if (c->sc_alloc && c->t == c->sc_ev.next && (rc = scalar_update(c))) return rc;
     if (c->tr_n > 0 && c->t == c->tr_ev.next && (rc = tracer_update(c))) return rc;
-    if (c->av_fields && c->t == c->av_ev.next) rc = average_update(c);
+    if (c->av_fields && c->t == c->av_ev.next && (rc = average_update(c))) return rc;
+    if (c->hi_n > 0 && c->t == c->hi_ev.next) rc = history_update(c);
     return rc;
 }
 
@@ -220,6 +284,8 @@ int iblb_set_tracers(iblb_ctx* c, long long n, const double* x, const double* y,
     if (n < 0) return fail(c, IBLB_ERR_ARG, "n is negative");
     if (stride < 1) return fail(c, IBLB_ERR_ARG, "stride must be >= 1");
     if (n > 0 && (!x || !y)) return fail(c, IBLB_ERR_ARG, "x or y is NULL");
+    if (c->hi_n > 0 && (c->hi_flags & IBLB_HIST_TRACERS))
+        return fail(c, IBLB_ERR_STATE, "iblb_set_tracers: the current history follows the tracers; remove the history first");
     if (!single_slab(c)) return group_refused(c, "iblb_set_tracers");
     int rc = check_positions(c, n, x, y);
     if (rc) return rc;
@@ -369,6 +435,144 @@ int iblb_average_info(iblb_ctx* c, iblb_window* w, unsigned* fields, int* stride
     return IBLB_OK;
 }
 
+// ---- history recorder -----------------------------------------------------------------------------------
+int iblb_set_history(iblb_ctx* c, long long n, const double* x, const double* y, unsigned fields, int stride,
+                     long long capacity, unsigned flags) {
+    if (!c) return IBLB_ERR_ARG;
+    if (flags & ~(unsigned)IBLB_HIST_TRACERS) return fail(c, IBLB_ERR_ARG, "flags: an unknown IBLB_HIST_* bit");
+    const bool follow = (flags & IBLB_HIST_TRACERS) != 0;
+    if (!follow && n < 0) return fail(c, IBLB_ERR_ARG, "n is negative");
+    const bool remove = !follow && n == 0;
+    int rc;
+    if (!remove) {
+        if (stride < 1) return fail(c, IBLB_ERR_ARG, "stride must be >= 1");
+        if (capacity < 1) return fail(c, IBLB_ERR_ARG, "capacity must be >= 1");
+        if (!follow && (!x || !y)) return fail(c, IBLB_ERR_ARG, "x or y is NULL");
+        if (fields & ~(IBLB_FIELD_ALL | IBLB_FIELD_SCALAR)) return fail(c, IBLB_ERR_ARG, "fields: an unknown IBLB_FIELD_* bit");
+        if (!follow && (rc = check_fields(c, fields))) return rc;
+        if (!single_slab(c)) return group_refused(c, "iblb_set_history");
+        if (!follow && (rc = check_positions(c, n, x, y))) return rc;
+        if ((rc = check_scalar_fields(c, fields))) return rc;
+        if (follow && c->tr_n == 0)
+            return fail(c, IBLB_ERR_STATE, "iblb_set_history: IBLB_HIST_TRACERS without tracers (iblb_set_tracers)");
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (remove) {
+        history_free(c);
+        return IBLB_OK;
+    }
+    // the new buffers first: a failed allocation leaves the previous history as it was
+    const long long np = follow ? c->tr_n : n;
+    const int planes = __builtin_popcount(fields) + (follow ? 3 : 0);
+    const long long limit = LLONG_MAX / (long long)sizeof(double);
+    if (np > limit / planes / 16 || capacity > (limit - (8LL * planes + 2) * np) / (planes * np))
+        return fail(c, IBLB_ERR_NOMEM, "iblb_set_history: the ring exceeds the address space");
+    const size_t e = (size_t)planes * (size_t)np;
+    const size_t ring = (size_t)capacity * e, total = ring + 8 * e + (follow ? 0 : 2 * (size_t)np);
+    DevBuf d;
+    HIP_TRY(c, hipMalloc(&d.p, total * sizeof(double)));
+    double* buf = (double*)d.p;
+    std::vector<long long> iter;
+    try {
+        iter.assign((size_t)capacity, 0);
+    } catch (const std::bad_alloc&) {
+        return fail(c, IBLB_ERR_NOMEM, "iblb_set_history: no host memory for the slots' iterations");
+    }
+    const std::vector<double> blank = history_stats_blank(e);
+    HIP_TRY(c, hipMemsetAsync(buf, 0, ring * sizeof(double), c->stream));
+    HIP_TRY(c, hipMemcpyAsync(buf + ring, blank.data(), 8 * e * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (!follow) {
+        HIP_TRY(c, hipMemcpyAsync(buf + ring + 8 * e, x, (size_t)np * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(buf + ring + 8 * e + np, y, (size_t)np * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    history_free(c);
+    c->hi_buf = buf;
+    d.p = nullptr;
+    c->hi_n = np;
+    c->hi_cap = capacity;
+    c->hi_fields = fields;
+    c->hi_flags = flags;
+    c->hi_planes = planes;
+    c->hi_iter.swap(iter);
+    c->hi_ev.stride = stride;
+    c->hi_ev.arm(c->t);
+    return IBLB_OK;
+}
+
+int iblb_reset_history(iblb_ctx* c) {
+    if (!c) return IBLB_ERR_ARG;
+    if (c->hi_n == 0) return fail(c, IBLB_ERR_STATE, "iblb_reset_history: no history is set");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t e = history_entries(c);
+    const std::vector<double> blank = history_stats_blank(e);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(history_stats_base(c), blank.data(), 8 * e * sizeof(double), hipMemcpyHostToDevice));
+    c->hi_ev.count = 0;
+    c->hi_ev.arm(c->t);
+    return IBLB_OK;
+}
+
+int iblb_get_history(iblb_ctx* c, long long first, long long count, double* out, long long* iterations) {
+    if (!c) return IBLB_ERR_ARG;
+    if (c->hi_n == 0) return fail(c, IBLB_ERR_STATE, "iblb_get_history: no history is set");
+    if (!out && !iterations) return fail(c, IBLB_ERR_ARG, "out and iterations are both NULL");
+    const long long recorded = c->hi_ev.count, oldest = std::max(0LL, recorded - c->hi_cap);
+    if (count < 0 || first < oldest || first > recorded || count > recorded - first)
+        return fail(c, IBLB_ERR_ARG, "records [first, first + count) are not all in the ring: need first >= max(0, recorded - "
+                                     "capacity), count >= 0, first + count <= recorded");
+    if (count == 0) return IBLB_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    // at most two contiguous runs of the ring: slots [s0, s0 + n1), then [0, count - n1)
+    const size_t e = history_entries(c);
+    const long long s0 = first % c->hi_cap, n1 = std::min(count, c->hi_cap - s0);
+    if (out) {
+        int rc = read_back(c, {{out, c->hi_buf + (size_t)s0 * e, (size_t)n1 * e * sizeof(double)},
+                               {out + (size_t)n1 * e, c->hi_buf, (size_t)(count - n1) * e * sizeof(double)}});
+        if (rc) return rc;
+    }
+    if (iterations)
+        for (long long r = 0; r < count; ++r) iterations[r] = c->hi_iter[(size_t)((first + r) % c->hi_cap)];
+    return IBLB_OK;
+}
+
+int iblb_get_history_stats(iblb_ctx* c, long long* count, long long* nonfinite, double* sum, double* sum_sq, double* min,
+                           double* max, long long* min_rec, long long* max_rec) {
+    if (!c) return IBLB_ERR_ARG;
+    if (c->hi_n == 0) return fail(c, IBLB_ERR_STATE, "iblb_get_history_stats: no history is set");
+    if (!count && !nonfinite && !sum && !sum_sq && !min && !max && !min_rec && !max_rec)
+        return fail(c, IBLB_ERR_ARG, "every output is NULL");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const HistoryStats s = history_stats(c);
+    const size_t nb = history_entries(c) * sizeof(double);
+    return read_back(c, {{count, s.count, nb}, {nonfinite, s.nonfinite, nb}, {sum, s.sum, nb}, {sum_sq, s.sum_sq, nb},
+                         {min, s.min, nb}, {max, s.max, nb}, {min_rec, s.min_rec, nb}, {max_rec, s.max_rec, nb}});
+}
+
+int iblb_get_history_points(iblb_ctx* c, double* x, double* y) {
+    if (!c) return IBLB_ERR_ARG;
+    if (c->hi_n == 0) return fail(c, IBLB_ERR_STATE, "iblb_get_history_points: no history is set");
+    if (c->hi_flags & IBLB_HIST_TRACERS)
+        return fail(c, IBLB_ERR_STATE, "iblb_get_history_points: the history follows the tracers (iblb_get_tracers)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t nb = (size_t)c->hi_n * sizeof(double);
+    return read_back(c, {{x, history_xy(c), nb}, {y, history_xy(c) + c->hi_n, nb}});
+}
+
+int iblb_history_info(iblb_ctx* c, long long* n, unsigned* fields, int* stride, long long* capacity, unsigned* flags,
+                      long long* recorded) {
+    if (!c) return IBLB_ERR_ARG;
+    const bool set = c->hi_n > 0;
+    if (n) *n = c->hi_n;
+    if (fields) *fields = c->hi_fields;
+    if (stride) *stride = set ? c->hi_ev.stride : 0;
+    if (capacity) *capacity = c->hi_cap;
+    if (flags) *flags = c->hi_flags;
+    if (recorded) *recorded = set ? c->hi_ev.count : 0;
+    return IBLB_OK;
+}
+
 // ---- passive scalar -----------------------------------------------------------------------------------
 int iblb_set_scalar(iblb_ctx* c, const iblb_scalar* cfg, const double* c0, const double* g0) {
     if (!c) return IBLB_ERR_ARG;
@@ -389,6 +593,9 @@ int iblb_set_scalar(iblb_ctx* c, const iblb_scalar* cfg, const double* c0, const
     if (!cfg && (c->av_fields & IBLB_FIELD_SCALAR))
         return fail(c, IBLB_ERR_STATE,
                     "iblb_set_scalar: the current average samples the scalar; remove or replace the average first");
+    if (!cfg && (c->hi_fields & IBLB_FIELD_SCALAR))
+        return fail(c, IBLB_ERR_STATE,
+                    "iblb_set_scalar: the current history records the scalar; remove or replace the history first");
     HIP_TRY(c, hipSetDevice(c->device));
     if (!cfg) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));

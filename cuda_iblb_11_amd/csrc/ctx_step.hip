@@ -713,7 +713,7 @@ int iblb_step(iblb_ctx* c, int nsteps) {
     int rc = check_ready(c);
     if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    // The observers (ctx_observe.hip: passive tracers, averaged fields, the passive scalar) cut the call at their event
+    // The observers (ctx_observe.hip: passive tracers, averaged fields, the passive scalar, the history) cut the call at their event
     // iterations: each piece (at most the smaller stride) is scheduled as a call of its own, then with that
     // state held fixed the observers due there run, as if the caller had stepped the piece, read the fields
     // and done their work on the host.  No observer: no event ahead, and the one piece is the whole call

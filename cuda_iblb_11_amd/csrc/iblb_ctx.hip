@@ -430,7 +430,7 @@ void iblb_destroy(iblb_ctx* c) {
     void* bufs[] = {c->g_alloc, c->cil_samples, c->cil_lasts, c->cil_bpoints, c->rho0, c->u0, c->force0, c->d_s,
                     c->d_us, c->d_Fs, c->d_eps, c->d_Fs_sum, c->fd_alloc, c->fl_alloc, c->d_Q, c->red_buf, c->d_sch_s,
                     c->d_sch_us, c->d_sch_eps, c->tr_x, c->tr_y, c->tr_laps, c->av_buf, c->sc_alloc,
-                    c->sc_src_field, c->sc_src_walls, c->sc_up, c->sc_end, c->sc_gau};
+                    c->sc_src_field, c->sc_src_walls, c->sc_up, c->sc_end, c->sc_gau, c->hi_buf};
     for (void* p : bufs)
         if (p) (void)hipFree(p);
     if (c->sig) (void)hipFree(c->sig);
@@ -525,6 +525,7 @@ int iblb_set_state(iblb_ctx* c, const double* rho, const double* u, const double
     c->tr_ev.arm(c->t);  // tracers stay; their updates count from the new state
     c->av_ev.arm(c->t);  // so do the averages: sums and counts kept, samples from the new state
     c->sc_ev.arm(c->t);  // and the scalar: populations and event count kept, the velocity from the new state
+    c->hi_ev.arm(c->t);  // and the history: records and statistics kept, the next record from the new state
     return IBLB_OK;
 }
 
@@ -941,6 +942,7 @@ int iblb_load_checkpoint(iblb_ctx* c, const char* path) {
     tracers_free(c);  // a checkpoint without an observer part holds no tracers,
     average_free(c);  // no averages
     scalar_free(c);   // and no scalar; with one, those it holds come back below
+    history_free(c);  // no checkpoint holds a history
     if (iv[CK_CILIA]) {
         iblb_cilia k{(int)iv[CK_CNUM], dv[CK_CSPACE], (int)iv[CK_CT], (int)iv[CK_CPSTEP]};
         if ((rc = iblb_set_cilia(c, &k))) return rc;

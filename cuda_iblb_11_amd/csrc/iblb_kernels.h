@@ -250,6 +250,27 @@ template <typename T>
 hipError_t launch_tracer_advect(const T* g, Layout L, Halo<T> H, const FieldsArgs& a, long n, int stride, double* x,
                                 double* y, int* laps, hipStream_t s);
 
+// History recorder (history_kernels.hip; include/iblb.h iblb_set_history): one lane per probe, its four cells
+// evaluated through point_eval.h exactly as launch_sample_points evaluates them.  The running statistics: eight
+// arrays of np * n entries each, entry k*n + p for plane k of a record at probe p.
+struct HistoryStats {
+    long long* count;
+    long long* nonfinite;
+    double* sum;
+    double* sum_sq;
+    double* min;
+    double* max;
+    long long* min_rec;
+    long long* max_rec;
+};
+// Record number m of n probes at (x[p], y[p]) into slot[k*n + p] and into the statistics, plane k the k-th set bit
+// of a.fields.  laps != nullptr: the probes are tracers, the record starts with the planes x, y, (double)laps and
+// a.fields may be 0.  A lone slab only, as launch_sample_points.
+template <typename T>
+hipError_t launch_history_record(const T* g, Layout L, Halo<T> H, const FieldsArgs& a, long n, const double* x,
+                                 const double* y, const int* laps, long long m, double* slot, const HistoryStats& s,
+                                 hipStream_t st);
+
 // Time- and phase-averaged fields (average_kernels.hip; include/iblb.h iblb_set_average).  One bin's
 // accumulators are `planes` planes of nxl * nyw doubles in the order the lanes run, [plane][il*nyw + j]:
 // the sums of the set bits of a.fields in ascending order, then their sums of squares (IBLB_AVG_SQ),

@@ -451,6 +451,92 @@ class Lattice:
         with np.errstate(invalid="ignore", divide="ignore"):
             return {m: v / float(a["samples"]) for m, v in a["sum"].items()}
 
+    # -- history: probe time series and tracer pathlines ------------------------------------------
+    def set_history(self, names=(), x=None, y=None, stride: int = 1, capacity: int = 1024,
+                    follow_tracers: bool = False) -> None:
+        """A record of the named fields at the probes (x, y) every `stride` iterations, kept in a ring of
+        `capacity` records on the device with running statistics per probe (iblb_set_history).
+        follow_tracers: the probes are the current tracers, x and y are ignored, every record also holds their
+        x, y and laps, and names may be empty (positions only).  A lone slab only; one history per lattice."""
+        names = [names] if isinstance(names, str) else list(names)
+        unknown = [n for n in names if n not in L.READ_FIELDS]
+        if unknown:
+            raise ValueError(f"fields must be chosen from {sorted(L.READ_FIELDS)}, got {names}")
+        bits = sum(L.READ_FIELDS[n] for n in set(names))
+        if follow_tracers:
+            self._check(self._lib.iblb_set_history(self._h, 0, None, None, bits, int(stride), int(capacity),
+                                                   L.HIST_TRACERS))
+            return
+        if x is None or y is None:
+            raise ValueError("x and y are needed unless follow_tracers is set")
+        x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+        y = np.ascontiguousarray(y, dtype=np.float64).ravel()
+        if x.size != y.size or x.size == 0:
+            raise ValueError("x and y must hold the same number of probes, at least one (remove_history removes)")
+        self._check(self._lib.iblb_set_history(self._h, x.size, _ptr(x), _ptr(y), bits, int(stride), int(capacity), 0))
+
+    def remove_history(self) -> None:
+        """Remove the history; `step` is then what it is without one."""
+        self._check(self._lib.iblb_set_history(self._h, 0, None, None, 0, 1, 1, 0))
+
+    def reset_history(self) -> None:
+        """Zero the record count and the statistics and keep the probes; the next record is number 0,
+        `stride` iterations from now (iblb_reset_history)."""
+        self._check(self._lib.iblb_reset_history(self._h))
+
+    def history_info(self) -> dict:
+        """{"n", "fields", "names", "stride", "capacity", "flags", "follow_tracers", "recorded", "planes"} of the
+        history (iblb_history_info); n == 0: none set.  planes: the plane names of a record in order."""
+        n, fields, stride = C.c_longlong(0), C.c_uint(0), C.c_int(0)
+        cap, flags, rec = C.c_longlong(0), C.c_uint(0), C.c_longlong(0)
+        self._check(self._lib.iblb_history_info(self._h, C.byref(n), C.byref(fields), C.byref(stride), C.byref(cap),
+                                                C.byref(flags), C.byref(rec)))
+        names = [m for m, b in L.READ_FIELDS.items() if fields.value & b]
+        follow = bool(flags.value & L.HIST_TRACERS)
+        return {"n": n.value, "fields": fields.value, "names": names, "stride": stride.value, "capacity": cap.value,
+                "flags": flags.value, "follow_tracers": follow, "recorded": rec.value,
+                "planes": (["x", "y", "laps"] if follow else []) + names if n.value else []}
+
+    def history(self, first=None, count=None) -> dict:
+        """Records [first, first + count) of the ring (iblb_get_history): {"iteration": (count,) int64, name:
+        (count, n) per recorded field, and "x", "y", "laps" (laps as float64) when following tracers}.  By
+        default everything the ring still holds; first alone: from there to the newest record."""
+        info = self.history_info()
+        if not info["n"]:
+            self._check(self._lib.iblb_get_history(self._h, 0, 0, None, None))
+        oldest = max(0, info["recorded"] - info["capacity"])
+        first = oldest if first is None else int(first)
+        count = info["recorded"] - first if count is None else int(count)
+        planes, n = info["planes"], info["n"]
+        out = np.empty((max(count, 0), len(planes), n))
+        it = np.zeros(max(count, 0), dtype=np.int64)
+        if count == 0 and oldest <= first <= info["recorded"]:
+            return {"iteration": it, **{m: out[:, k, :] for k, m in enumerate(planes)}}
+        self._check(self._lib.iblb_get_history(self._h, first, count, _ptr(out), _ptr(it)))
+        return {"iteration": it, **{m: out[:, k, :] for k, m in enumerate(planes)}}
+
+    def history_stats(self) -> dict:
+        """The running statistics over every record since the set or the last reset (iblb_get_history_stats):
+        {plane name: {"count", "nonfinite", "sum", "sum_sq", "min", "max", "min_rec", "max_rec"}}, each [n]."""
+        info = self.history_info()
+        if not info["n"]:
+            self._check(self._lib.iblb_get_history_stats(self._h, None, None, None, None, None, None, None, None))
+        planes, n = info["planes"], info["n"]
+        kinds = {"count": np.int64, "nonfinite": np.int64, "sum": np.float64, "sum_sq": np.float64,
+                 "min": np.float64, "max": np.float64, "min_rec": np.int64, "max_rec": np.int64}
+        arr = {k: np.zeros((len(planes), n), dtype=t) for k, t in kinds.items()}
+        self._check(self._lib.iblb_get_history_stats(self._h, *(_ptr(a) for a in arr.values())))
+        return {m: {k: a[j] for k, a in arr.items()} for j, m in enumerate(planes)}
+
+    def history_points(self) -> tuple[np.ndarray, np.ndarray]:
+        """The fixed probes x [n], y [n] (iblb_get_history_points); an error when following tracers."""
+        n = self.history_info()["n"]
+        x, y = np.empty(n), np.empty(n)
+        if n == 0:
+            self._check(self._lib.iblb_get_history_points(self._h, None, None))
+        self._check(self._lib.iblb_get_history_points(self._h, _ptr(x), _ptr(y)))
+        return x, y
+
     # -- passive scalar ---------------------------------------------------------------------------
     def set_scalar(self, c0=None, g0=None, tau: float = 1.0, stride: int = 1,
                    walls=((L.SCALAR_WALL_NOFLUX, 0.0), (L.SCALAR_WALL_NOFLUX, 0.0))) -> None:

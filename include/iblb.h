@@ -433,6 +433,80 @@ int iblb_get_average(iblb_ctx* ctx, int bin, double* sum, double* sum_sq, double
 int iblb_average_info(iblb_ctx* ctx, iblb_window* w, unsigned* fields, int* stride, int* nbins, unsigned* flags,
                       long long* samples_total);
 
+/* History: time series at chosen points that the context itself records on the device while iblb_step runs, so
+ * that the velocity at a probe over a beat, the concentration at a sensor over a release, or the paths the tracers
+ * took need no readback per sample and keep the deep sweep between records.  The tracers, the averages and the
+ * scalar hold the present moment or a sum over time; this observer keeps the sequence: a ring of `capacity`
+ * records on the device, per-probe running statistics beside it, and any stretch of records back in one copy.
+ * One history per context.  flags: */
+#define IBLB_HIST_TRACERS 1   /* the positions are the context's tracers (pathlines) */
+/* iblb_set_history without IBLB_HIST_TRACERS: x, y [n], n >= 1, are fixed probes, validated exactly as
+ * iblb_sample_points validates them and copied to the device; `fields` is what iblb_sample_points accepts and must
+ * not be 0 (IBLB_FIELD_VORT included: the observer runs on a lone slab only).  A record is np = popcount(fields)
+ * planes of n doubles, plane k the k-th set bit (ascending).
+ * With IBLB_HIST_TRACERS: x, y and n are ignored, the probes are the tracers set at the call (n = their count;
+ * none set: IBLB_ERR_STATE), and `fields` may be 0, positions only.  Every record then starts with three more
+ * planes before the field planes, x, y and (double)laps, so np = 3 + popcount(fields).  While such a history is
+ * set iblb_set_tracers returns IBLB_ERR_STATE and changes nothing, whether it would replace or remove the
+ * tracers: remove the history first.
+ * Both: stride >= 1, capacity >= 1, no flag but the one above.  A negative n, a NULL x or y with n > 0, fields == 0
+ * without the flag, an unknown field bit or flag, stride < 1, capacity < 1, YDIM < 2, or a point out of range or
+ * non-finite: IBLB_ERR_ARG, checked before anything is touched.  A slab of a local or RCCL group:
+ * IBLB_ERR_UNSUPPORTED.  A scalar bit (IBLB_FIELD_C, _CUX, _CUY) without a scalar: IBLB_ERR_STATE.  n == 0
+ * without the flag removes the history (the other arguments are then not looked at, and a slab of a group may do
+ * it too), and iblb_step is then exactly what it is without one.  A set replaces any previous history; the new
+ * buffers are allocated before the old ones are freed, and any error, IBLB_ERR_NOMEM included, leaves the previous
+ * history as it was.  A successful set starts `recorded` and the statistics at zero and records
+ * t0 = iblb_get_step.  The ring takes capacity * np * n doubles on the device, the statistics 8 * np * n more.
+ * Record rule.  After the iterations t0 + stride, t0 + 2 stride, ... the context takes record number
+ * m = 0, 1, 2, ... of the state of that iteration into slot m % capacity of the ring; the iteration of each slot
+ * is kept on the host.  Plane k at probe p holds the bits iblb_sample_points returns at that moment for that field
+ * at that probe's position; under IBLB_HIST_TRACERS the three leading planes hold the bits iblb_get_tracers
+ * returns and the field planes are sampled at those positions.  iblb_step(nsteps) with a history cuts the call at
+ * the record iterations and schedules each piece (at most `stride` iterations) as a call of its own; the result is
+ * by definition that of the caller doing iblb_step(piece), then iblb_sample_points (iblb_get_tracers), then
+ * appending on the host.  Records count on across calls.  With other observers set the call is cut at the union
+ * of the event sets, and at a common iteration the history runs last: the scalar's event, the tracers' update,
+ * the averages' sample, then the record.  A pathline record therefore holds the positions after that iteration's
+ * update, and a sample of C follows that iteration's event.  A scalar bit needs the scalar at every record:
+ * iblb_set_scalar(cfg == NULL) returns IBLB_ERR_STATE meanwhile, replacing the scalar is allowed and the history
+ * goes on with the new one.  A stride >= K (IBLB_SWEEP_DEPTH) keeps the deep sweep between records; stride 1
+ * costs the one-step path at every iteration.  One record is one launch on the context's stream, one lane per
+ * probe, without a host synchronise.
+ * Running statistics, per plane and probe, updated by the same launch in record order, over every record since
+ * the set or the last reset, those the ring has overwritten included.  In double, one rounding per operation, no
+ * contraction, nothing compensated.  A finite v of record m:  count += 1;  sum = sum + v;  sum_sq = sum_sq + v*v;
+ * v < min: min = v, min_rec = m;  v > max: max = v, max_rec = m.  A non-finite v only does nonfinite += 1.  With
+ * nothing seen min = +inf, max = -inf and both record numbers are -1.
+ * iblb_get_history returns the records [first, first + count) into out[((r*np) + k)*n + p], r counted from
+ * `first`, and their iterations into iterations[r]; either pointer may be NULL, not both.  It needs
+ * first >= max(0, recorded - capacity), count >= 0 and first + count <= recorded; otherwise IBLB_ERR_ARG and
+ * nothing is written.  It does not drain the ring (a record stays until the ring overwrites it) and copies at
+ * most two contiguous runs of it.
+ * iblb_get_history_stats: every array is [np * n], index k*n + p; any pointer may be NULL, not all.
+ * iblb_get_history_points returns the fixed probes, x [n] and y [n] (either may be NULL); under IBLB_HIST_TRACERS
+ * IBLB_ERR_STATE (the positions are iblb_get_tracers').
+ * iblb_reset_history zeroes `recorded` and the statistics, keeps the positions and the ring's size, and sets t0 to
+ * the current step (the next record is number 0, `stride` iterations later).
+ * iblb_history_info returns n, fields, stride, capacity, flags and the records taken since the set or the last
+ * reset (any pointer may be NULL); no history set: n = 0 and the rest zero.  The getters and the reset then return
+ * IBLB_ERR_STATE.
+ * iblb_set_state keeps the history, its records and statistics, and re-bases t0 to the new state's step count 0:
+ * the next record follows `stride` iterations later, and its iteration counts from the new state.  iblb_destroy
+ * frees it.  No checkpoint holds a history, neither iblb_save_checkpoint nor iblb_save_checkpoint_ex (whose
+ * observer bits stay the three they are): a caller drains the ring before saving and sets the history afresh after
+ * loading.  iblb_load_checkpoint removes it, as it removes every observer.  A context that joins a group after the
+ * set fails its next record with IBLB_ERR_UNSUPPORTED, as the scalar does. */
+int iblb_set_history(iblb_ctx* ctx, long long n, const double* x, const double* y, unsigned fields, int stride,
+                     long long capacity, unsigned flags);
+int iblb_get_history(iblb_ctx* ctx, long long first, long long count, double* out, long long* iterations);
+int iblb_get_history_stats(iblb_ctx* ctx, long long* count, long long* nonfinite, double* sum, double* sum_sq,
+                           double* min, double* max, long long* min_rec, long long* max_rec);
+int iblb_get_history_points(iblb_ctx* ctx, double* x, double* y);
+int iblb_reset_history(iblb_ctx* ctx);
+int iblb_history_info(iblb_ctx* ctx, long long* n, unsigned* fields, int* stride, long long* capacity,
+                      unsigned* flags, long long* recorded);
+
 /* Passive scalar: one concentration field C that the context itself advects with the fluid and diffuses while
  * iblb_step runs, so that transport and mixing (a solute cleared by the cilia, uptake at a wall) need neither a
  * readback of u per iteration nor a solver on the host.  A D2Q5 BGK advection-diffusion lattice: five populations
