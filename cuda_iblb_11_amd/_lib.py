@@ -98,6 +98,16 @@ HIST_TRACERS = 1
 # wall kinds of iblb_set_scalar
 SCALAR_WALL_NOFLUX = 0
 SCALAR_WALL_VALUE = 1
+# wall kinds and statuses of iblb_set_tracer_model
+TRACER_WALLS = {"clamp": 0, "reflect": 1, "absorb": 2}
+TRACER_ALIVE = 0
+TRACER_AT_BOTTOM = 1
+TRACER_AT_TOP = 2
+
+
+class TracerModel(C.Structure):
+    """struct iblb_tracer_model (include/iblb.h)."""
+    _fields_ = [("diffusivity", C.c_double), ("drift", C.c_double * 2), ("wall", C.c_int * 2), ("seed", C.c_ulonglong)]
 
 
 class Scalar(C.Structure):
@@ -208,6 +218,10 @@ _SIGS = {
     "iblb_set_tracers": ([_vp, C.c_longlong, _vp, _vp, C.c_int], C.c_int),
     "iblb_get_tracers": ([_vp, _vp, _vp, _vp], C.c_int),
     "iblb_tracer_count": ([_vp, C.POINTER(C.c_longlong), C.POINTER(C.c_int), C.POINTER(C.c_longlong)], C.c_int),
+    "iblb_set_tracer_model": ([_vp, C.POINTER(TracerModel), _vp, _vp], C.c_int),
+    "iblb_tracer_model_info": ([_vp, C.POINTER(TracerModel), C.POINTER(C.c_int), C.POINTER(C.c_longlong)], C.c_int),
+    "iblb_get_tracer_fates": ([_vp, _vp, _vp], C.c_int),
+    "iblb_get_tracer_deposits": ([_vp, _vp, _vp], C.c_int),
     "iblb_set_average": ([_vp, C.POINTER(Window), C.c_uint, C.c_int, C.c_int, C.c_uint], C.c_int),
     "iblb_reset_average": ([_vp], C.c_int),
     "iblb_get_average": ([_vp, C.c_int, _vp, _vp, _vp, C.POINTER(C.c_longlong)], C.c_int),

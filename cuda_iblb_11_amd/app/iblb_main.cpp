@@ -29,6 +29,15 @@
 // x = (i + 0.5) XDIM / nx_t, y = (j + 0.5) (YDIM - 1) / ny_t, tracer i * ny_t + j, updated every `stride` (default 1)
 // iterations, and writes <it>-tracers.dat beside the fluid files at every output iteration (BigData or not): one line
 // x  y  laps per tracer, lattice units, %.17g.  Checkpoints hold the tracers: a restarted run goes on with them.
+// IBLB_PARTICLES=D[,drift_y[,bottom[,top[,seed]]]] (needs IBLB_TRACERS) puts a motion model on that grid
+// (iblb_set_tracer_model): the tracers also jitter with the diffusivity D >= 0 (lattice units), settle with the velocity
+// drift_y (default 0) along y, and meet the bottom and the top wall as clamp|reflect|absorb says (default
+// absorb,reflect); seed (default 0) selects the random numbers.  At every output iteration, beside <it>-tracers.dat
+// (which keeps its format), <it>-fates.dat holds one line per tracer and <it>-deposits.dat one line per column (%.17g),
+//   index  status  iteration  x  y          x  bottom  top
+// status 0 alive, 1 at the bottom, 2 at the top, `iteration` the one at which the tracer deposited (-1 while alive);
+// bottom and top the tracers deposited in that column.  No checkpoint holds the model or the fates: under IBLB_RESTART
+// the model is set afresh on the restored tracers with every tracer alive.
 // IBLB_PROBES=nx_p,ny_p[,stride] (one GPU) lets the context record time series (iblb_set_history) at a regular
 // nx_p x ny_p grid of probes, x = (i + 0.5) XDIM / nx_p, y = (j + 0.5) (YDIM - 1) / ny_p, probe i * ny_p + j, one
 // record every `stride` (default 1) iterations: u_x, u_y, and C as well with IBLB_SCALAR.  The ring holds
@@ -294,6 +303,56 @@ int main(int argc, char* argv[]) {
             if (lead) cerr << "IBLB_PROBES and IBLB_PATHLINES are both set: a context records one history (iblb_set_history)" << endl;
             return 2;
         }
+    }
+
+    // the tracers' motion model (extension): a diffusivity, a settling velocity along y, a kind per wall and a seed
+    bool pa_on = false;
+    iblb_tracer_model pa_model{0., {0., 0.}, {IBLB_TRACER_WALL_ABSORB, IBLB_TRACER_WALL_REFLECT}, 0ull};
+    if (const char* ps = getenv("IBLB_PARTICLES"); ps && *ps) {
+        // one to five parts separated by commas, nothing else
+        std::vector<std::string> parts(1);
+        for (const char* p = ps; *p; ++p) {
+            if (*p == ',') parts.emplace_back();
+            else parts.back() += *p;
+        }
+        bool ok = parts.size() <= 5;
+        for (size_t n = 0; ok && n < parts.size() && n < 2; ++n) {  // D >= 0 and drift_y, both finite
+            const char* p = parts[n].c_str();
+            char* end = nullptr;
+            errno = 0;
+            const double v = strtod(p, &end);
+            ok = ((*p >= '0' && *p <= '9') || *p == '.' || *p == '+' || *p == '-') && end != p && *end == 0 &&
+                 errno == 0 && std::isfinite(v) && (n == 1 || v >= 0.);
+            (n == 0 ? pa_model.diffusivity : pa_model.drift[1]) = v;
+        }
+        for (size_t n = 2; ok && n < parts.size() && n < 4; ++n) {
+            if (parts[n] == "clamp") pa_model.wall[n - 2] = IBLB_TRACER_WALL_CLAMP;
+            else if (parts[n] == "reflect") pa_model.wall[n - 2] = IBLB_TRACER_WALL_REFLECT;
+            else if (parts[n] == "absorb") pa_model.wall[n - 2] = IBLB_TRACER_WALL_ABSORB;
+            else ok = false;
+        }
+        if (ok && parts.size() == 5) {
+            const char* p = parts[4].c_str();
+            char* end = nullptr;
+            errno = 0;
+            pa_model.seed = strtoull(p, &end, 10);
+            ok = *p >= '0' && *p <= '9' && end != p && *end == 0 && errno == 0;
+        }
+        if (!ok) {
+            if (lead)
+                cerr << "IBLB_PARTICLES must be D[,drift_y[,bottom[,top[,seed]]]] with D >= 0 and drift_y finite, bottom "
+                        "and top in clamp|reflect|absorb and seed a non-negative integer, got " << ps << endl;
+            return 2;
+        }
+        if (world > 1) {  // the particles are the tracers: a lone slab only (include/iblb.h)
+            if (lead) cerr << "IBLB_PARTICLES is not available under a launcher (WORLD_SIZE > 1): run on one GPU" << endl;
+            return 2;
+        }
+        if (tr_nx == 0) {
+            if (lead) cerr << "IBLB_PARTICLES needs IBLB_TRACERS: the particles are the tracers under a motion model" << endl;
+            return 2;
+        }
+        pa_on = true;
     }
 
     // time- and phase-averaged fields (extension): sample stride, 0 = off
@@ -617,6 +676,11 @@ int main(int argc, char* argv[]) {
         if ((rc = iblb_set_tracers(ctx, (long long)tr_n, tr_x.data(), tr_y.data(), tr_stride)))
             return die(ctx, rc, "iblb_set_tracers");
     }
+    // the motion model on those tracers; no checkpoint holds it or the fates: a restarted run sets it afresh on the
+    // tracers its checkpoint held, every one alive
+    std::vector<int> pa_status(pa_on ? tr_n : 0);
+    std::vector<long long> pa_hit(pa_on ? tr_n : 0), pa_dep(pa_on ? 2 * (size_t)XDIM : 0);
+    if (pa_on && (rc = iblb_set_tracer_model(ctx, &pa_model, nullptr, nullptr))) return die(ctx, rc, "iblb_set_tracer_model");
     // averaged fields: rho, u_x, u_y with their squares and u_x u_y on every av_sx-th column and av_sy-th row,
     // from the run's first iteration (a restarted run's too, unless its checkpoint held averages: those go on, and
     // the run's first output iteration lies before the checkpoint)
@@ -918,6 +982,29 @@ int main(int argc, char* argv[]) {
                 }
                 for (size_t k = 0; k < tr_n; k++) fprintf(ft, "%.17g\t%.17g\t%d\n", tr_x[k], tr_y[k], tr_laps[k]);
                 fclose(ft);
+            }
+            if (pa_on) {  // (tr_x, tr_y: read just above)
+                if ((rc = iblb_get_tracer_fates(ctx, pa_status.data(), pa_hit.data())))
+                    return die(ctx, rc, "iblb_get_tracer_fates");
+                if ((rc = iblb_get_tracer_deposits(ctx, pa_dep.data(), pa_dep.data() + XDIM)))
+                    return die(ctx, rc, "iblb_get_tracer_deposits");
+                outfile = raw_data + to_string(it) + "-fates.dat";
+                FILE* ff = fopen(outfile.c_str(), "w");
+                if (!ff) {
+                    fprintf(stderr, "cannot write %s: %s\n", outfile.c_str(), strerror(errno));
+                    return 1;
+                }
+                for (size_t k = 0; k < tr_n; k++)
+                    fprintf(ff, "%zu\t%d\t%lld\t%.17g\t%.17g\n", k, pa_status[k], pa_hit[k], tr_x[k], tr_y[k]);
+                fclose(ff);
+                outfile = raw_data + to_string(it) + "-deposits.dat";
+                FILE* fd = fopen(outfile.c_str(), "w");
+                if (!fd) {
+                    fprintf(stderr, "cannot write %s: %s\n", outfile.c_str(), strerror(errno));
+                    return 1;
+                }
+                for (unsigned int i = 0; i < XDIM; i++) fprintf(fd, "%u\t%lld\t%lld\n", i, pa_dep[i], pa_dep[XDIM + i]);
+                fclose(fd);
             }
             if (sc_tau > 0.) {
                 if ((rc = iblb_get_scalar(ctx, &sc_win, sc_out.data()))) return die(ctx, rc, "iblb_get_scalar");

@@ -199,6 +199,14 @@ struct iblb_ctx {
     int* tr_laps = nullptr;
     long long tr_n = 0;
     iblbh::Periodic tr_ev;  // count: updates done since iblb_set_tracers
+    // the tracers' motion model (iblb_set_tracer_model).  tr_status == nullptr: none, the plain update runs.
+    // tr_status [tr_n] IBLB_TRACER_ALIVE / _AT_BOTTOM / _AT_TOP, tr_hit [tr_n] the hit iteration (-1 while alive),
+    // tr_dep [2 ncol] the scratch of the per-column deposit counts (bottom, top), tr_amp = sqrt(6 D stride)
+    int* tr_status = nullptr;
+    long long* tr_hit = nullptr;
+    unsigned long long* tr_dep = nullptr;
+    iblb_tracer_model tr_model{};
+    double tr_amp = 0.0;
     // time- and phase-averaged fields (iblb_set_average).  av_fields == 0: none.  With averaging iblb_step
     // stops at the iterations of av_ev and adds a sample to bin av_ev.count % av_nbins there.
     // av_buf: [av_nbins][av_planes][av_win.nx * av_win.ny] doubles, a plane in the order the accumulate

@@ -100,7 +100,19 @@ static ScalarGauges scalar_gauges(const iblb_ctx* c) {
     return ScalarGauges{idx, idx + c->ncol, t, t + ns, t + 2 * ns, t + 2 * ns + nl};
 }
 
+// the tracers' motion model (iblb_set_tracer_model): the tracers then take the plain update again
+static void tracer_model_free(iblb_ctx* c) {
+    for (void* p : {(void*)c->tr_status, (void*)c->tr_hit, (void*)c->tr_dep})
+        if (p) (void)hipFree(p);
+    c->tr_status = nullptr;
+    c->tr_hit = nullptr;
+    c->tr_dep = nullptr;
+    c->tr_model = iblb_tracer_model{};
+    c->tr_amp = 0.0;
+}
+
 void tracers_free(iblb_ctx* c) {
+    tracer_model_free(c);  // the model belongs to the tracer set it was put on
     for (void* p : {(void*)c->tr_x, (void*)c->tr_y, (void*)c->tr_laps})
         if (p) (void)hipFree(p);
     c->tr_x = c->tr_y = nullptr;
@@ -156,12 +168,18 @@ static size_t average_bin_elems(const iblb_ctx* c) {
 }
 
 // One update of the tracers from the current state, on the context's stream: the state prepared as
-// for a reader (the band streams joined, the owed IB force evaluated), then one launch.
+// for a reader (the band streams joined, the owed IB force evaluated), then one launch: the plain kernel, or with
+// a motion model (iblb_set_tracer_model) the particles'.
 static int tracer_update(iblb_ctx* c) {
     int rc = band_join(c);
     if (rc || (rc = prepare_read(c))) return rc;
     const FieldsArgs a = point_args(c, IBLB_FIELD_UX | IBLB_FIELD_UY);
+    const iblb_tracer_model& k = c->tr_model;
+    const ParticleStep P{{k.drift[0], k.drift[1]}, c->tr_amp, {k.wall[0], k.wall[1]}, k.seed, c->tr_ev.count, c->t};
     HIP_TRY(c, with_state(c, [&](auto* g, auto H) {
+        if (c->tr_status)
+            return launch_particle_advect(g, c->L, H, a, (long)c->tr_n, c->tr_ev.stride, P, c->tr_x, c->tr_y, c->tr_laps,
+                                          c->tr_status, c->tr_hit, c->stream);
         return launch_tracer_advect(g, c->L, H, a, (long)c->tr_n, c->tr_ev.stride, c->tr_x, c->tr_y, c->tr_laps, c->stream);
     }));
     c->tr_ev.advance();
@@ -331,6 +349,109 @@ int iblb_tracer_count(iblb_ctx* c, long long* n, int* stride, long long* updates
     if (n) *n = c->tr_n;
     if (stride) *stride = c->tr_ev.stride;
     if (updates) *updates = c->tr_ev.count;
+    return IBLB_OK;
+}
+
+// ---- the tracers' motion model ----------------------------------------------------------------------
+int iblb_set_tracer_model(iblb_ctx* c, const iblb_tracer_model* m, const int* status0, const long long* iteration0) {
+    if (!c) return IBLB_ERR_ARG;
+    if (m) {
+        if (!(std::isfinite(m->diffusivity) && m->diffusivity >= 0.0))
+            return fail(c, IBLB_ERR_ARG, "iblb_set_tracer_model: diffusivity must be finite and >= 0");
+        if (!(std::isfinite(m->drift[0]) && std::isfinite(m->drift[1])))
+            return fail(c, IBLB_ERR_ARG, "iblb_set_tracer_model: drift must be finite");
+        for (int w : {m->wall[0], m->wall[1]})
+            if (w != IBLB_TRACER_WALL_CLAMP && w != IBLB_TRACER_WALL_REFLECT && w != IBLB_TRACER_WALL_ABSORB)
+                return fail(c, IBLB_ERR_ARG, "iblb_set_tracer_model: wall: an unknown IBLB_TRACER_WALL_* kind");
+        if ((status0 == nullptr) != (iteration0 == nullptr))
+            return fail(c, IBLB_ERR_ARG, "iblb_set_tracer_model: status0 and iteration0 go together: both or neither");
+    }
+    if (c->tr_n == 0) return fail(c, IBLB_ERR_STATE, "iblb_set_tracer_model: no tracers are set (iblb_set_tracers)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (!m) {
+        tracer_model_free(c);
+        return IBLB_OK;
+    }
+    const size_t np = (size_t)c->tr_n;
+    std::vector<int> st(np, IBLB_TRACER_ALIVE);
+    std::vector<long long> hit(np, -1);
+    if (status0) {
+        std::vector<double> y(np);
+        HIP_TRY(c, hipMemcpy(y.data(), c->tr_y, np * sizeof(double), hipMemcpyDeviceToHost));
+        const double ytop = (double)(c->ny - 1);
+        for (size_t p = 0; p < np; ++p) {
+            const int s = status0[p];
+            if (s != IBLB_TRACER_ALIVE && s != IBLB_TRACER_AT_BOTTOM && s != IBLB_TRACER_AT_TOP)
+                return fail(c, IBLB_ERR_ARG, "iblb_set_tracer_model: status0[" + std::to_string(p) + "] is not an IBLB_TRACER_* status");
+            if (s != IBLB_TRACER_ALIVE && y[p] != (s == IBLB_TRACER_AT_BOTTOM ? 0.0 : ytop))
+                return fail(c, IBLB_ERR_ARG, "iblb_set_tracer_model: status0[" + std::to_string(p) + "] is deposited, but the tracer is not on that wall's row");
+            st[p] = s;
+            if (s != IBLB_TRACER_ALIVE) hit[p] = iteration0[p];
+        }
+    }
+    // the new arrays first: a failed allocation leaves the previous model and fates as they were
+    DevBuf ds, dh, dd;
+    HIP_TRY(c, hipMalloc(&ds.p, np * sizeof(int)));
+    HIP_TRY(c, hipMalloc(&dh.p, np * sizeof(long long)));
+    HIP_TRY(c, hipMalloc(&dd.p, 2 * (size_t)c->ncol * sizeof(unsigned long long)));
+    HIP_TRY(c, hipMemcpy(ds.p, st.data(), np * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(dh.p, hit.data(), np * sizeof(long long), hipMemcpyHostToDevice));
+    tracer_model_free(c);
+    c->tr_status = (int*)ds.p;
+    c->tr_hit = (long long*)dh.p;
+    c->tr_dep = (unsigned long long*)dd.p;
+    ds.p = dh.p = dd.p = nullptr;
+    c->tr_model = *m;
+    c->tr_amp = std::sqrt(6.0 * m->diffusivity * (double)c->tr_ev.stride);
+    return IBLB_OK;
+}
+
+// the per-column deposit counts of both walls, counted on the device: host [2 ncol], bottom then top
+static int tracer_deposit_counts(iblb_ctx* c, std::vector<unsigned long long>* host) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, launch_particle_deposit((long)c->tr_n, c->ncol, c->tr_x, c->tr_status, c->tr_dep, c->stream));
+    host->resize(2 * (size_t)c->ncol);
+    return read_back(c, host->data(), c->tr_dep, host->size() * sizeof(unsigned long long));
+}
+
+int iblb_tracer_model_info(iblb_ctx* c, iblb_tracer_model* m, int* present, long long counts[3]) {
+    if (!c) return IBLB_ERR_ARG;
+    long long k[3] = {0, 0, 0};
+    if (counts && c->tr_status) {
+        std::vector<unsigned long long> dep;
+        int rc = tracer_deposit_counts(c, &dep);
+        if (rc) return rc;
+        for (int i = 0; i < c->ncol; ++i) {
+            k[1] += (long long)dep[i];
+            k[2] += (long long)dep[(size_t)c->ncol + i];
+        }
+        k[0] = c->tr_n - k[1] - k[2];
+    }
+    if (m) *m = c->tr_model;
+    if (present) *present = c->tr_status ? 1 : 0;
+    if (counts) std::copy(k, k + 3, counts);
+    return IBLB_OK;
+}
+
+int iblb_get_tracer_fates(iblb_ctx* c, int* status, long long* iteration) {
+    if (!c) return IBLB_ERR_ARG;
+    if (!c->tr_status) return fail(c, IBLB_ERR_STATE, "iblb_get_tracer_fates: no model is set (iblb_set_tracer_model)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t np = (size_t)c->tr_n;
+    return read_back(c, {{status, c->tr_status, np * sizeof(int)}, {iteration, c->tr_hit, np * sizeof(long long)}});
+}
+
+int iblb_get_tracer_deposits(iblb_ctx* c, long long* bottom, long long* top) {
+    if (!c) return IBLB_ERR_ARG;
+    if (!c->tr_status) return fail(c, IBLB_ERR_STATE, "iblb_get_tracer_deposits: no model is set (iblb_set_tracer_model)");
+    std::vector<unsigned long long> dep;
+    int rc = tracer_deposit_counts(c, &dep);
+    if (rc) return rc;
+    for (int i = 0; i < c->ncol; ++i) {
+        if (bottom) bottom[i] = (long long)dep[i];
+        if (top) top[i] = (long long)dep[(size_t)c->ncol + i];
+    }
     return IBLB_OK;
 }
 

@@ -429,7 +429,7 @@ void iblb_destroy(iblb_ctx* c) {
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     void* bufs[] = {c->g_alloc, c->cil_samples, c->cil_lasts, c->cil_bpoints, c->rho0, c->u0, c->force0, c->d_s,
                     c->d_us, c->d_Fs, c->d_eps, c->d_Fs_sum, c->fd_alloc, c->fl_alloc, c->d_Q, c->red_buf, c->d_sch_s,
-                    c->d_sch_us, c->d_sch_eps, c->tr_x, c->tr_y, c->tr_laps, c->av_buf, c->sc_alloc,
+                    c->d_sch_us, c->d_sch_eps, c->tr_x, c->tr_y, c->tr_laps, c->tr_status, c->tr_hit, c->tr_dep, c->av_buf, c->sc_alloc,
                     c->sc_src_field, c->sc_src_walls, c->sc_up, c->sc_end, c->sc_gau, c->hi_buf};
     for (void* p : bufs)
         if (p) (void)hipFree(p);

@@ -250,6 +250,27 @@ template <typename T>
 hipError_t launch_tracer_advect(const T* g, Layout L, Halo<T> H, const FieldsArgs& a, long n, int stride, double* x,
                                 double* y, int* laps, hipStream_t s);
 
+// Tracers with a motion model (particle_kernels.hip; include/iblb.h iblb_set_tracer_model): the constants of one
+// update.  amp = sqrt(6 D stride), m = the updates done before this one, t = the iteration of this one.
+struct ParticleStep {
+    double drift[2];
+    double amp;
+    int wall[2];
+    unsigned long long seed;
+    long long m, t;
+};
+// One update of the alive ones of n tracers over `stride` iterations with the state held fixed: the sample of
+// launch_tracer_advect, the drift, a counter-based random step and the walls.  status and hit are written
+// only where a tracer deposits.
+template <typename T>
+hipError_t launch_particle_advect(const T* g, Layout L, Halo<T> H, const FieldsArgs& a, long n, int stride,
+                                  const ParticleStep& P, double* x, double* y, int* laps, int* status, long long* hit,
+                                  hipStream_t s);
+// dep[floor(x[p])] += 1 for every tracer at the bottom, dep[ncol + floor(x[p])] += 1 for every one at the top;
+// dep [2 ncol] is zeroed on the stream first.
+hipError_t launch_particle_deposit(long n, int ncol, const double* x, const int* status, unsigned long long* dep,
+                                   hipStream_t s);
+
 // History recorder (history_kernels.hip; include/iblb.h iblb_set_history): one lane per probe, its four cells
 // evaluated through point_eval.h exactly as launch_sample_points evaluates them.  The running statistics: eight
 // arrays of np * n entries each, entry k*n + p for plane k of a record at probe p.

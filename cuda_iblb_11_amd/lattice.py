@@ -392,6 +392,54 @@ class Lattice:
         self._check(self._lib.iblb_get_tracers(self._h, _ptr(x), _ptr(y), _ptr(laps)))
         return x, y, laps
 
+    # -- the tracers' motion model: particles -----------------------------------------------------
+    def set_tracer_model(self, diffusivity: float = 0.0, drift=(0, 0), walls=("clamp", "clamp"), seed: int = 0,
+                         status=None, iteration=None) -> None:
+        """Particles: the current tracers also jitter (a uniform random step of variance 2 * diffusivity *
+        stride per update), settle with the velocity `drift` and meet the bottom and top wall as `walls` says
+        ("clamp", "reflect" or "absorb": the tracer deposits and never moves again) (iblb_set_tracer_model).
+        status, iteration: the fates to start from, as `tracer_fates` returned them; neither: all alive."""
+        unknown = [w for w in walls if w not in L.TRACER_WALLS]
+        if unknown or len(walls) != 2:
+            raise ValueError(f"walls must be two of {sorted(L.TRACER_WALLS)}, got {walls}")
+        m = L.TracerModel(float(diffusivity), (C.c_double * 2)(float(drift[0]), float(drift[1])),
+                          (C.c_int * 2)(L.TRACER_WALLS[walls[0]], L.TRACER_WALLS[walls[1]]), int(seed) & (2**64 - 1))
+        st = None if status is None else np.ascontiguousarray(status, dtype=np.int32).ravel()
+        it = None if iteration is None else np.ascontiguousarray(iteration, dtype=np.int64).ravel()
+        n = self.tracer_info()["n"]
+        if any(a is not None and a.size != n for a in (st, it)):
+            raise ValueError(f"status and iteration must hold one entry per tracer ({n})")
+        self._check(self._lib.iblb_set_tracer_model(self._h, C.byref(m), _ptr(st), _ptr(it)))
+
+    def remove_tracer_model(self) -> None:
+        """The tracers take the plain update again (iblb_set_tracer_model with no model)."""
+        self._check(self._lib.iblb_set_tracer_model(self._h, None, None, None))
+
+    def tracer_model_info(self) -> dict:
+        """{"present", "diffusivity", "drift", "walls", "seed", "alive", "at_bottom", "at_top"} of the tracers'
+        model (iblb_tracer_model_info); present False: none set."""
+        m, present, counts = L.TracerModel(), C.c_int(0), (C.c_longlong * 3)()
+        self._check(self._lib.iblb_tracer_model_info(self._h, C.byref(m), C.byref(present), counts))
+        names = {v: k for k, v in L.TRACER_WALLS.items()}
+        return {"present": bool(present.value), "diffusivity": m.diffusivity, "drift": (m.drift[0], m.drift[1]),
+                "walls": (names[m.wall[0]], names[m.wall[1]]), "seed": m.seed,
+                "alive": counts[0], "at_bottom": counts[1], "at_top": counts[2]}
+
+    def tracer_fates(self) -> tuple[np.ndarray, np.ndarray]:
+        """status [n] (int32: 0 alive, 1 at the bottom, 2 at the top) and the hit iteration [n] (int64, -1 while
+        alive) of the tracers under a model (iblb_get_tracer_fates)."""
+        n = self.tracer_info()["n"]
+        status, iteration = np.zeros(n, dtype=np.int32), np.full(n, -1, dtype=np.int64)
+        self._check(self._lib.iblb_get_tracer_fates(self._h, _ptr(status), _ptr(iteration)))
+        return status, iteration
+
+    def tracer_deposits(self) -> tuple[np.ndarray, np.ndarray]:
+        """bottom [nx], top [nx] (int64): the deposited tracers of each wall per column floor(x), counted on
+        the device (iblb_get_tracer_deposits)."""
+        bottom, top = np.zeros(self.nx, dtype=np.int64), np.zeros(self.nx, dtype=np.int64)
+        self._check(self._lib.iblb_get_tracer_deposits(self._h, _ptr(bottom), _ptr(top)))
+        return bottom, top
+
     # -- time- and phase-averaged fields --------------------------------------------------------
     def set_average(self, names, window=None, stride: int = 1, nbins: int = 1, squares: bool = False,
                     uxuy: bool = False) -> None:

@@ -382,6 +382,74 @@ int iblb_get_tracers(iblb_ctx* ctx, double* x, double* y, int* laps);   /* [n] e
 /* Tracers set, their stride and the updates done since iblb_set_tracers (any may be NULL). */
 int iblb_tracer_count(iblb_ctx* ctx, long long* n, int* stride, long long* updates);
 
+/* A motion model and a fate for the tracers: particles (a dust grain, a droplet, a bacterium) that the flow
+ * carries, that jitter by Brownian motion, settle with a drift velocity and deposit on a wall.  On the device
+ * the model adds status[n] in int and the hit iteration[n] in long long to the tracers' arrays; a context
+ * without a model runs the plain update above, launch for launch. */
+#define IBLB_TRACER_WALL_CLAMP   0   /* as the plain tracers: y clamped to the wall's row          */
+#define IBLB_TRACER_WALL_REFLECT 1   /* specular: the overshoot is folded back                      */
+#define IBLB_TRACER_WALL_ABSORB  2   /* the tracer deposits where its step crossed the wall's row   */
+#define IBLB_TRACER_ALIVE     0
+#define IBLB_TRACER_AT_BOTTOM 1
+#define IBLB_TRACER_AT_TOP    2
+
+typedef struct iblb_tracer_model {
+    double diffusivity;          /* D >= 0, lattice units                              */
+    double drift[2];             /* settling velocity added to the fluid's, finite     */
+    int    wall[2];              /* IBLB_TRACER_WALL_* of the bottom [0] and top [1]   */
+    unsigned long long seed;
+} iblb_tracer_model;
+
+/* iblb_set_tracer_model puts the model on the tracers currently set (m == NULL removes it; without one that is
+ * IBLB_OK).  status0, iteration0 [n], both or neither: the fates to start from, as iblb_get_tracer_fates
+ * returned them, so that a caller can put back the fates it read before a save and go on; both NULL: every
+ * tracer alive.  The positions, laps, the schedule and the update count are those of the tracers and are not
+ * touched.  No tracers set: IBLB_ERR_STATE.  A negative or non-finite diffusivity, a non-finite drift or an
+ * unknown wall kind: IBLB_ERR_ARG, checked before anything is touched; only one of status0 / iteration0, a status
+ * outside {0, 1, 2}, or a deposited status whose tracer's y is not on that wall's row (0, or YDIM-1):
+ * IBLB_ERR_ARG.  Every error leaves the previous model and fates untouched.  (The hit iteration of an alive
+ * tracer is stored as -1 whatever iteration0 holds for it.)
+ * Update rule.  At the tracers' update iterations, for every tracer with status IBLB_TRACER_ALIVE; s =
+ * (double)stride, m = the updates done before this one (iblb_tracer_count's `updates`), t = the iteration
+ * (iblb_get_step), p = the tracer's index.  Double arithmetic throughout, one rounding per operation, no
+ * contraction.
+ *  1. (ux, uy) = the bilinear sample of the plain rule.  Non-finite: the tracer is unchanged and stays alive.
+ *  2. Counter-based random numbers, so that a run cut into calls, restarted or re-based draws the same numbers;
+ *     64-bit unsigned integers that wrap:
+ *       mix(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31
+ *       key  = mix(seed + 0x9E3779B97F4A7C15 * (p + 1))
+ *       r_k  = mix(key + 0x9E3779B97F4A7C15 * (2 m + k + 1)),  k = 0 for x, k = 1 for y
+ *       xi_k = (double)(r_k >> 11) * 2^-52 - 1.0,  in [-1, 1) and exact
+ *     The step is uniform, not Gaussian: its variance per update is amp^2 / 3 = 2 D stride, and the central
+ *     limit theorem does the rest; no device log or cos appears whose last bits a host would not reproduce.
+ *  3. amp = sqrt(6.0 * D * s), computed once on the host;
+ *       xn = (x + s*(ux + drift[0])) + amp*xi_0,   yn = (y + s*(uy + drift[1])) + amp*xi_1
+ *     (with D == 0 the random terms are skipped, which gives the same bits).
+ *  4. Walls.  Bottom if yn < 0 (yw = 0), top if yn > YDIM-1 (yw = YDIM-1):
+ *       CLAMP:    yn = yw
+ *       REFLECT:  yn = -yn, respectively yn = yw - (yn - yw), then clamped into [0, YDIM-1]
+ *       ABSORB:   lam = (yw - y)/(yn - y);  xn = x + lam*(xn - x);  yn = yw;  status = IBLB_TRACER_AT_BOTTOM /
+ *                 IBLB_TRACER_AT_TOP, hit iteration = t
+ *  5. x wraps with laps exactly as in the plain rule, on the final xn; still outside after one wrap: x and laps
+ *     stay, y and the status still take effect.
+ * So a deposited tracer never moves again, a stored position is always finite and in range, and a model with
+ * D = 0, zero drift and both walls CLAMP gives the plain tracers bit for bit.
+ * The model belongs to the tracer set it was put on: iblb_set_tracers (replace or remove) and iblb_load_checkpoint
+ * remove it; iblb_set_state keeps it with the fates and the update count, as it keeps the tracers.  No checkpoint
+ * holds the model or the fates: IBLB_CKPT_TRACERS writes the bytes it writes without a model.  A history under
+ * IBLB_HIST_TRACERS records a deposited tracer's resting place again and again.
+ * iblb_tracer_model_info: the model (zeroes without one), whether one is set, and counts[3] = the tracers alive,
+ * at the bottom, at the top (zeroes without one); any may be NULL.
+ * iblb_get_tracer_fates: status [n] and hit iteration [n] (-1 while alive), either may be NULL.
+ * iblb_get_tracer_deposits: bottom [XDIM], top [XDIM], either may be NULL: the deposited tracers of each wall
+ * per column floor(x), counted on the device (integer atomics: exact whatever the order), so that O(XDIM)
+ * integers are copied out instead of the tracers.  Both without a model: IBLB_ERR_STATE. */
+int iblb_set_tracer_model(iblb_ctx* ctx, const iblb_tracer_model* m,
+                          const int* status0, const long long* iteration0);
+int iblb_tracer_model_info(iblb_ctx* ctx, iblb_tracer_model* m, int* present, long long counts[3]);
+int iblb_get_tracer_fates(iblb_ctx* ctx, int* status, long long* iteration);
+int iblb_get_tracer_deposits(iblb_ctx* ctx, long long* bottom, long long* top);
+
 /* Time- and phase-averaged fields: sums of chosen fields over a window that the context itself accumulates
  * on the device while iblb_step runs, so that a beat average (the mean flow, its fluctuation <u'u'>, the flow
  * at a given phase of the beat) needs no readback per sample and keeps the deep sweep between samples.
