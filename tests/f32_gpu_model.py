@@ -16,6 +16,12 @@ round-3 order (rho * constant, rho * (c.u)), which this emulation reproduces at 
 round-3 errors (K1 128^2, 1000 iterations: rho - 1 1.8e-4, u_x 1.2e-6, u_y 8.9e-5).
 `dtype=np.float64` runs the same operation order in double (what the order itself costs, without
 float32); `mutate` seeds one named error into the collide (MUTATIONS), for the regime tests' power check.
+
+F32GpuIBChannel adds the immersed-boundary iteration (csrc/ib_device.h, lbm_kernels.hip) in the
+kernels' arithmetic: the force of an iteration from the stored post-collision state (the kernels' pull,
+then Store<float>::to_f), node terms and the F_s fold in the reference's order and float rounding, the
+spread in double, and the collide of a forced cell with constants folded from (float)(g + F).  Its
+seeded errors are IB_MUTATIONS.
 """
 from __future__ import annotations
 
@@ -195,3 +201,167 @@ class F32GpuChannel:
         ux = (mx + 0.5 * float(self.k["Fx"])) / rho
         uy = (my + 0.5 * float(self.k["Fy"])) / rho
         return rho.ravel(), np.concatenate([ux.ravel(), uy.ravel()])
+
+
+# ---- the immersed boundary -----------------------------------------------------------------------------
+# Seeded one-term errors (`mutate` of F32GpuIBChannel) of the IB kernels, for the power check of the IB
+# regime tests (tests/test_regimes.py::test_regimes_ib_discriminate).  A forced cell is one that a point's
+# spread reached in this iteration.
+IB_MUTATIONS = {
+    "I1": "a forced cell's collide constants from the IB force alone ((float)(0 + F): the body force dropped)",
+    "I2": "a forced cell's (c.u)(c.F) part (hE) from the body force alone",
+    "I3": "node_term with rho taken as 1: 2 delta (u_s - m)",
+    "I4": "nodes at x = -1 and x = XDIM read by a same-row periodic wrap instead of the flat index",
+    "I5": "the F/2 of the velocity correction from the body force alone (j_x, j_y of a forced cell's collide, the reader's u)",
+    "I6": "the spread at the points of the next iteration (off by one in a moving schedule)",
+}
+
+
+def d_delta(xs, ys, x, y):
+    """d_delta (iblb_device.h:513-531; ImmersedBoundary.cu:21-81) on arrays: xs, ys float32, x, y integer.
+    |x - xs| in float32, each 1-D factor in double rounded to float32, their product in float32."""
+    def factor(xs, x):
+        dx = np.abs(np.asarray(x).astype(f32) - xs)
+        near, inside = dx <= f32(0.5), dx <= f32(1.5)
+        dd = np.where(inside, dx, f32(0)).astype(f64)
+        a = np.where(near, 0.33333, 0.16667)
+        b = np.where(near, 1.0, 5.0 - 3.0 * dd)
+        c = np.where(near, 1.0, -1.0)
+        d = np.where(near, dd, np.where(inside, f32(1) - dx, f32(0)).astype(f64))
+        return np.where(inside, a * (b + c * np.sqrt(-3.0 * d * d + 1.0)), 0.0).astype(f32)
+    return factor(xs, x) * factor(ys, y)
+
+
+def lifted_moments(g):
+    """Store<T>::to_f of the pulled state ((double)h + w_i) and moments<double> of it (iblb_device.h:119-124):
+    rho = f0 + ... + f8 in that order, m = sum c f in the reference's order."""
+    f = pull(g).astype(f64) + WD[:, None, None]
+    r = f[0]
+    for i in range(1, 9):
+        r = r + f[i]
+    mx = ((((f[1] - f[3]) + f[5]) - f[6]) - f[7]) + f[8]
+    my = ((((f[2] - f[4]) + f[5]) + f[6]) - f[7]) - f[8]
+    return r, mx, my
+
+
+class F32GpuIBChannel(F32GpuChannel):
+    """The channel with Lagrangian points: `points` is (s, u_s, epsilon) (epsilon may be None) or
+    points(it) for the points set before iteration `it` (0-based), as Simulation.set_lagrangian takes them.
+
+    Iteration: collide-stream with the force of the previous iteration (the boot iteration with the body
+    force), then the force of the new state from the points of this iteration: what ib_point_kernel /
+    ib_ghost_kernel / ib_next_group evaluate from the stored post-collision state before the next collide,
+    and the readers at the end of a call.  F_s and the float32 product F delta are float32 in both
+    precisions, as in the kernels; dtype is the storage and collide type.
+
+    spread_order: a permutation of the points, the order in which their terms reach a cell (the kernels:
+    the arrival order of fp64 atomics).  perturb: a seed; every forced cell's cast force (float)(g + F) is
+    moved by one ulp of the compute type up or down, seeded signs, in every iteration (the most a
+    different arrival order can do to what the collide reads).  mutate: IB_MUTATIONS."""
+
+    def __init__(self, nx, ny, tau, tau2, rho, u, body_force, points, dtype=np.float32, mutate=None,
+                 spread_order=None, perturb=None):
+        assert mutate is None or mutate in IB_MUTATIONS, mutate
+        super().__init__(nx, ny, tau, tau2, rho, u, body_force, dtype=dtype)
+        self.tau, self.tau2, self.dtype, self.ib_mutate = tau, tau2, dtype, mutate
+        self.gx, self.gy = float(body_force[0]), float(body_force[1])
+        self.points = points if callable(points) else (lambda it: points)
+        self.order = None if spread_order is None else np.asarray(spread_order)
+        self.rng = None if perturb is None else np.random.default_rng(perturb)
+        self.it = 0
+        self.fd = np.zeros((2, ny, nx))          # the dense IB force (without the body force)
+        self.forced = np.zeros((ny, nx), bool)   # cells a spread term reached
+        self.F_s = np.zeros(0, f32)
+
+    def _points(self, it):
+        s, us, eps = self.points(it)
+        s, us = np.asarray(s, f32), np.asarray(us, f32)
+        eps = np.ones(s.size // 2, np.int32) if eps is None else np.asarray(eps, np.int32)
+        return s[0::2], s[1::2], us[0::2], us[1::2], eps
+
+    @staticmethod
+    def _nodes(xs, ys):
+        """Node n of every point: (x, y) = (nearbyint(xs), nearbyint(ys)) + c_n, and its delta."""
+        x = np.rint(xs.astype(f64)).astype(np.int64)[:, None] + CX[None, :]
+        y = np.rint(ys.astype(f64)).astype(np.int64)[:, None] + CY[None, :]
+        return x, y, d_delta(xs[:, None], ys[:, None], x, y)
+
+    def _force(self, it):
+        """node_term, the F_s fold and spread_node (ib_device.h) on the stored state."""
+        nx, ny, m = self.nx, self.ny, self.ib_mutate
+        xs, ys, usx, usy, eps = self._points(it)
+        x, y, dl = self._nodes(xs, ys)
+        j = y * nx + x  # flat index without wrap: column j % XDIM of row j / XDIM, left out beyond the lattice
+        valid, xj, yj = (j >= 0) & (j < nx * ny), j % nx, j // nx
+        if m == "I4":
+            edge = (x == -1) | (x == nx)
+            valid = np.where(edge, (y >= 0) & (y < ny), valid)
+            xj, yj = np.where(edge, x % nx, xj), np.where(edge, y, yj)
+        xj, yj = np.where(valid, xj, 0), np.where(valid, yj, 0)
+        r, mx, my = (a[yj, xj] for a in lifted_moments(self.g))
+        d2 = 2.0 * dl.astype(f64)
+        if m == "I3":
+            tx, ty = d2 * (usx.astype(f64)[:, None] - mx), d2 * (usy.astype(f64)[:, None] - my)
+        else:
+            tx = d2 * r * (usx.astype(f64)[:, None] - mx / r)
+            ty = d2 * r * (usy.astype(f64)[:, None] - my / r)
+        Fx, Fy = np.zeros(xs.size, f32), np.zeros(xs.size, f32)
+        for n in range(9):  # fold_terms: node order, each partial sum rounded to float32
+            Fx = np.where(valid[:, n], (Fx.astype(f64) + tx[:, n]).astype(f32), Fx)
+            Fy = np.where(valid[:, n], (Fy.astype(f64) + ty[:, n]).astype(f32), Fy)
+        self.F_s = np.stack([Fx, Fy], axis=1).ravel()
+        if m == "I6":
+            xs, ys, _, _, eps = self._points(it + 1)
+            x, y, dl = self._nodes(xs, ys)
+        # spread_node: clipped to the lattice (no periodic image), skipped where epsilon or delta is 0
+        ok = (eps[:, None] != 0) & (x >= 0) & (x < nx) & (y >= 0) & (y < ny) & (dl != 0)
+        e = eps.astype(f64)[:, None]
+        px = (Fx[:, None] * dl).astype(f64) * 1.0 * e  # the float32 product, then double
+        py = (Fy[:, None] * dl).astype(f64) * 1.0 * e
+        o = np.arange(xs.size) if self.order is None else self.order
+        ok_o = ok[o]
+        self.fd = np.zeros((2, ny, nx))
+        np.add.at(self.fd[0], (y[o][ok_o], x[o][ok_o]), px[o][ok_o])  # in the points' order, in double
+        np.add.at(self.fd[1], (y[o][ok_o], x[o][ok_o]), py[o][ok_o])
+        self.forced = np.zeros((ny, nx), bool)
+        self.forced[y[ok], x[ok]] = True
+
+    def _constants(self):
+        """The collide constants per cell: make_kforce<R>(kb, (R)(gx + fx), (R)(gy + fy)); a cell without
+        IB force gets (R)(gx + 0.0) = (R)gx, the body-force constants bit for bit."""
+        R, m, forced = self.dtype, self.ib_mutate, self.forced
+        Fx, Fy = (self.gx + self.fd[0]).astype(R), (self.gy + self.fd[1]).astype(R)
+        if m == "I1":
+            Fx, Fy = np.where(forced, self.fd[0].astype(R), Fx), np.where(forced, self.fd[1].astype(R), Fy)
+        if self.rng is not None:
+            sx, sy = self.rng.choice([-np.inf, np.inf], size=(2,) + forced.shape).astype(R)
+            Fx, Fy = np.where(forced, np.nextafter(Fx, sx), Fx), np.where(forced, np.nextafter(Fy, sy), Fy)
+        k = kconst(self.tau, self.tau2, Fx, Fy, dtype=R)
+        if m == "I2":
+            for p in range(4):
+                k[f"hE{p}"] = np.where(forced, self.k[f"hE{p}"], k[f"hE{p}"])
+        if m == "I5":
+            k["hFx"], k["hFy"] = np.where(forced, self.k["hFx"], k["hFx"]), np.where(forced, self.k["hFy"], k["hFy"])
+        return k
+
+    def step(self, n=1):
+        for _ in range(n):
+            if self.booted:
+                self.g = relax(pull(self.g), self._constants(), self.variant)
+            self.booted = True  # (the boot collide of __init__ is the first iteration)
+            self._force(self.it)
+            self.it += 1
+
+    def macro(self):
+        """rho, u = (m + (F_dense + g)/2)/rho in float64 from the stored state (macro_out_kernel)."""
+        r, mx, my = lifted_moments(self.g)
+        fx, fy = (0.0, 0.0) if self.ib_mutate == "I5" else self.fd
+        ux, uy = (mx + 0.5 * (fx + self.gx)) / r, (my + 0.5 * (fy + self.gy)) / r
+        return r.ravel(), np.concatenate([ux.ravel(), uy.ravel()])
+
+    def force(self):
+        """The dense force with the body force, as iblb_get_force returns it."""
+        return np.concatenate([(self.fd[0] + self.gx).ravel(), (self.fd[1] + self.gy).ravel()])
+
+    def lagrangian_force(self):
+        return self.F_s
